@@ -23,16 +23,21 @@ Workloads (BASELINE.json configs):
     xlate             NCO mixer alone
     fir63             63-tap FIR (the reference BlackmanWindow design of configs[0])
 
-Rank 0 prints ONE JSON line (contract in the task statement) extended with
+A plain run sets up, spins up and warms up, times the K steps, writes the last step's outputs if --dump-outputs is given,
+and rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) extended with
   "roofline":     dominant kernel vs the HBM roofline: algorithmic bytes per launch / mean
-                  launch duration (HIP events on the launch stream, measured here)
+                  launch duration (HIP events on the launch stream around the K timed steps)
   "roofline_fp32": the same launch vs the FP32 vector peak (the direct-form 256-tap FIR is
                   compute-bound: 1024 FLOP / 16 B per sample)
+--full measures and checks the rest, in the same line (the --no-* options leave legs out):
+  "roofline.kernel_ms_isolated": the dominant kernel once more, --kernel-iters launches on their own
+  "rccl.halo_check_max_rel_err": N > 1: a fresh operator fed the predecessor's tail must reproduce this rank's head
   "block_call":   N = 1 only: per-call time of the same operator on ONE reference-sized block (1e6 samples, the most the
                   reference's stream API hands over per call, stream.h:7), 200 back-to-back calls -- latency-bound, not
                   part of `value`.
-  "chain":        default run only: the fused xlating-FIR + decimate-by-8 chain (BASELINE configs[2]) timed by the same
+  "chain":        default workload only: the fused xlating-FIR + decimate-by-8 chain (BASELINE configs[2]) timed by the same
                   protocol right behind the FIR, with its own roofline object
+  "channelizer", "channelizer_m8": default workload only: BASELINE configs[4], 64 channels, decimation 64 and 8, likewise
   "cpu_baseline": the CPU oracle timed on this host's cores, N = 1 only: scalar VOLK-generic order on all worker
                   threads (`value`), a SIMD-lane FMA variant (`value_simd`), and one block-graph worker thread
                   source -> FIR -> NullSink (`value_1thread_graph`).
@@ -53,6 +58,8 @@ if ROOT not in sys.path:
 CHAN_ROW_PAD = 32           # samples between the end of a channel row and the start of the next (see run_workload)
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 FP32_PEAK_TFLOPS = 157.3   # FP32 vector == FP32 MFMA peak (same file)
+DUMP_BYTES = 32 << 20      # --dump-outputs: all files of one run together, shared evenly by the legs and ranks
+DUMP_SEED = 20251016       # which elements --dump-outputs samples from an output larger than its share
 
 # algorithmic bytes / flops per INPUT sample
 WORKLOADS = {
@@ -280,6 +287,13 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="fir256", choices=sorted(WORKLOADS))
     ap.add_argument("--log2n", type=int, default=27, help="input samples per GPU per step = 2^log2n")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the isolated kernel time, the multi-rank halo "
+                         "self-check, the fir256 run's chain and channelizer legs, `block_call` and `cpu_baseline` (the --no-* options "
+                         "below take legs out of such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what each timed leg computed in its last step to DIR/<workload>.npy "
+                         "(float32; complex samples as [..., 2] re/im pairs; a seeded sample of larger outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=14.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-block-call", action="store_true",
@@ -295,7 +309,10 @@ def parse_args(argv=None):
     ap.add_argument("--spinup-ms", type=float, default=200.0,
                     help="untimed device spin-up before the W warmup steps: the GPU needs ~50 launches (~25 ms) "
                          "for its clocks to settle under this load; the timed region is still exactly K steps")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -385,7 +402,7 @@ def run_workload(name: str, args, ctx) -> dict:
         c_ring.set_timing(True)
 
     def step():
-        ring.step(x, out, next_x=x)
+        return ring.step(x, out, next_x=x)
 
     def restart():
         """Operator and ring back to the start of the stream (after the communication-free spin-up)."""
@@ -410,10 +427,10 @@ def run_workload(name: str, args, ctx) -> dict:
         step()
     torch.cuda.synchronize()
 
-    # Halo check (outside the timed region, no oracle): a fresh operator fed the predecessor's
+    # Halo check (--full, outside the timed region, no oracle): a fresh operator fed the predecessor's
     # regenerated tail + my head must reproduce my head.
     halo_err = None
-    if world > 1 and H:
+    if args.full and world > 1 and H:
         pos_now = ring.stream_position()
         step()
         torch.cuda.synchronize()
@@ -448,7 +465,7 @@ def run_workload(name: str, args, ctx) -> dict:
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(args.steps):
-        step()
+        y = step()
     ev1.record()
     torch.cuda.synchronize()
     ctrl_barrier()                     # (drains the exchange prefetched for a step that does not run, then the barrier)
@@ -456,6 +473,8 @@ def run_workload(name: str, args, ctx) -> dict:
     kms_timed = ev0.elapsed_time(ev1) / args.steps
     dt = ctrl_reduce(dt)
     dbg("timed loop done")
+    if args.dump_outputs:
+        dump_output(y, os.path.join(args.dump_outputs, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), ctx["dump_bytes"])
     ring.drain()
     rccl = None
     if world > 1 or self_ring:
@@ -474,7 +493,8 @@ def run_workload(name: str, args, ctx) -> dict:
             "halo_bytes": H * 8,
             "halo_check_max_rel_err": halo_err,
             "halo_check": ("fresh operator + regenerated predecessor tail vs this rank's output head, max over ranks" if halo_err is not None
-                           else "not run (one rank: its own tail is its halo; tests/test_gpu_ring.py compares that stream with the oracle)"),
+                           else "not run (one rank: its own tail is its halo; tests/test_gpu_ring.py compares that stream with the oracle)"
+                           if world == 1 else "not run (--full runs it)"),
             "exchange_us_mean": round(ctrl_reduce(xus.get("mean_us", 0.0)), 2),
             "exchange_us_max": round(ctrl_reduce(xus.get("max_us", 0.0)), 2),
             "exchanges_timed": xus.get("exchanges"),
@@ -485,9 +505,9 @@ def run_workload(name: str, args, ctx) -> dict:
     ms_per_step = dt / args.steps * 1e3
     value = world * n / (dt / args.steps) / 1e6
 
-    # The same kernel once more on its own (args.kernel_iters back-to-back launches, no ring bookkeeping between them): reported as
-    # kernel_ms_isolated; `roofline` is computed from the launches of the timed region.
-    kms_iso = op.time_dev(x, out, args.kernel_iters)
+    # --full: the same kernel once more on its own (args.kernel_iters back-to-back launches, no ring bookkeeping between them),
+    # reported as kernel_ms_isolated; `roofline` is computed from the launches of the timed region.
+    kms_iso = op.time_dev(x, out, args.kernel_iters) if args.full else None
     kinfo = op.last_kernel()
     kms = kms_timed
     torch.cuda.synchronize()
@@ -546,7 +566,7 @@ def run_workload(name: str, args, ctx) -> dict:
             "kernel": kinfo["name"],
             "kernel_ms": round(kms, 4),
             "kernel_ms_source": "HIP events around the K timed steps (one launch per step per GPU)",
-            "kernel_ms_isolated": round(kms_iso, 4),
+            **({"kernel_ms_isolated": round(kms_iso, 4)} if kms_iso is not None else {}),
             "algorithmic_bytes_per_sample": w["bytes"],
             "launch": {"grid": kinfo["grid"], "block": kinfo["block"], "lds_bytes": kinfo["lds_bytes"]},
         },
@@ -575,9 +595,28 @@ def run_workload(name: str, args, ctx) -> dict:
         except Exception:
             pass
     op.close()
-    del x, out
+    del x, out, y
     torch.cuda.empty_cache()
     return res
+
+
+def dump_output(y, path: str, max_bytes: int) -> None:
+    """--dump-outputs: `y` (what the operator's caller received from the last timed step) as float32 .npy, complex samples as
+    [..., 2] re/im pairs.  An output of more than `max_bytes` is sampled: one element at a seeded offset inside each of k equal runs
+    of the flattened output, so that two runs with the same arguments store the same elements."""
+    import numpy as np
+    import torch
+
+    total = y.numel()
+    k = min(total, max(1, max_bytes // y.element_size()))
+    if k < total:
+        run = total // k
+        idx = np.arange(k, dtype=np.int64) * run + np.random.default_rng(DUMP_SEED).integers(0, run, k)
+        ti = torch.from_numpy(idx).to(y.device)
+        y = y[ti // y.shape[1], ti % y.shape[1]] if y.dim() == 2 else y[ti]
+    a = y.reshape(-1).cpu()
+    a = torch.view_as_real(a) if a.is_complex() else a
+    np.save(path, a.numpy().astype(np.float32, copy=False))
 
 
 def block_call(name: str, ctx) -> dict:
@@ -643,7 +682,20 @@ def main():
             dist.init_process_group("gloo", rank=rank, world_size=world)
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-    ctx = dict(world=world, rank=rank, local_rank=local_rank, dev=dev, rehearse=rehearse, self_ring=self_ring)
+    legs = [args.workload]
+    if args.full and args.workload == "fir256" and not args.no_chain:
+        # the metric's name says "FIR+decimate chain": the fused xlating FIR + decimate-by-8 (BASELINE configs[2]) is
+        # timed by the same protocol (W warmup, K steps, barrier + synchronize on both sides, max over ranks) right
+        # behind the FIR and reported in the same line
+        legs.append("xlate_fir_decim8")
+        if not args.no_channelizer:
+            # BASELINE configs[4]: the 64-channel channelizer on one stream, critically sampled (decimation 64) and its M = 8 variant
+            # (SURVEY 8d config 5), by the same protocol
+            legs += ["chan64", "chan64m8"]
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+    ctx = dict(world=world, rank=rank, local_rank=local_rank, dev=dev, rehearse=rehearse, self_ring=self_ring,
+               dump_bytes=DUMP_BYTES // (len(legs) * world))
     if world > 1:
         # Control plane (barriers, the max-over-ranks clock, the ring's id broadcast) on gloo: the only RCCL communicator with
         # traffic in this process is then the halo ring's.  If gloo cannot be had (every rank fails alike: one host), the default
@@ -658,19 +710,9 @@ def main():
                 ctx.update(ctrl=None, ctrl_dev=dev, ctrl_name="default nccl group (no gloo)")
 
     res = run_workload(args.workload, args, ctx)
-    chain = None
-    if args.workload == "fir256" and not args.no_chain:
-        # the metric's name says "FIR+decimate chain": the fused xlating FIR + decimate-by-8 (BASELINE configs[2]) is
-        # timed by the same protocol (W warmup, K steps, barrier + synchronize on both sides, max over ranks) right
-        # behind the FIR and reported in the same line
-        chain = run_workload("xlate_fir_decim8", args, ctx)
-
-    chan = chan8 = None
-    if args.workload == "fir256" and not args.no_chain and not args.no_channelizer:
-        # BASELINE configs[4]: the 64-channel channelizer on one stream, critically sampled (decimation 64) and its M = 8 variant
-        # (SURVEY 8d config 5), by the same protocol
-        chan = run_workload("chan64", args, ctx)
-        chan8 = run_workload("chan64m8", args, ctx)
+    chain = run_workload("xlate_fir_decim8", args, ctx) if "xlate_fir_decim8" in legs[1:] else None
+    chan = run_workload("chan64", args, ctx) if "chan64" in legs[1:] else None
+    chan8 = run_workload("chan64m8", args, ctx) if "chan64m8" in legs[1:] else None
 
     if rank == 0:
         line = {
@@ -707,12 +749,12 @@ def main():
                              "steps": args.steps, "warmup": args.warmup, "config": leg["config"], "roofline": leg["roofline"],
                              "hbm_roofline_msps": leg["hbm_roofline_msps"], "frac_of_hbm_roofline_msps": leg["frac_of_hbm_roofline_msps"],
                              **({"rccl": leg["rccl"]} if "rccl" in leg else {})}
-        if world == 1 and not args.no_block_call:
+        if args.full and world == 1 and not args.no_block_call:
             # what a block of the reference's graph gets per call (latency-bound: DESIGN.md section 5, EXPERIMENTS.md "Reference-sized calls")
             line["block_call"] = block_call(args.workload, ctx)
             if chain is not None:
                 line["chain"]["block_call"] = block_call("xlate_fir_decim8", ctx)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds)
         print(json.dumps(line), flush=True)
 

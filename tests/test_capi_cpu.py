@@ -103,6 +103,35 @@ def test_bench_starts_its_own_ranks_before_touching_the_gpu(monkeypatch):
     assert body.index("launch_ranks(args)") < body.index("import torch")     # nothing GPU-related runs first
 
 
+def test_bench_dump_output_sample(tmp_path):
+    """bench.py --dump-outputs: an output within its byte share is written whole; a larger one as the same seeded sample on every
+    call, one element inside each equal run of the flattened output (a channelizer's rows are a strided view: the padding between
+    them is never read), complex samples as float32 re/im pairs."""
+    import importlib
+    import sys
+
+    import torch
+
+    sys.path.insert(0, ROOT) if ROOT not in sys.path else None
+    bench = importlib.import_module("bench")
+    base = torch.full((64, 1032), -1.0, dtype=torch.float32)
+    base[:, :1000] = torch.arange(64 * 1000, dtype=torch.float32).reshape(64, 1000)
+    y = torch.complex(base, -base)[:, :1000]
+    bench.dump_output(y, str(tmp_path / "whole.npy"), 1 << 20)
+    w = np.load(tmp_path / "whole.npy")
+    assert w.dtype == np.float32 and w.shape == (64000, 2)
+    assert np.array_equal(w[:, 0], np.arange(64000, dtype=np.float32)) and np.array_equal(w[:, 1], -w[:, 0])
+    bench.dump_output(y, str(tmp_path / "a.npy"), 8000)
+    bench.dump_output(y, str(tmp_path / "b.npy"), 8000)
+    a, b = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    assert a.dtype == np.float32 and a.shape == (1000, 2) and np.array_equal(a, b)
+    idx = a[:, 0].astype(np.int64)
+    assert np.array_equal(idx // 64, np.arange(1000)) and np.array_equal(a[:, 1], -a[:, 0])
+    bench.dump_output(torch.arange(100, dtype=torch.float32), str(tmp_path / "r.npy"), 100)
+    r = np.load(tmp_path / "r.npy")
+    assert r.dtype == np.float32 and r.shape == (25,) and np.array_equal(r.astype(np.int64) // 4, np.arange(25))
+
+
 def test_no_kernel_uses_scratch():
     """profiles/r04_resource_usage.txt (scripts/resource_usage.py: hipcc's kernel-resource-usage remarks for every kernel instantiation
     of the shipped library) was made from the sources as they are now, and no kernel has scratch memory or spilled VGPRs

@@ -240,7 +240,7 @@ def test_bench_two_ranks_rehearsal_end_to_end():
     """`python bench.py --gpus 2` with no launcher: it starts torch.distributed.run itself (a child, before touching the GPU),
     both ranks share cuda:0 (QDSP_BENCH_REHEARSE=1: halos over gloo, RCCL refuses two ranks on one device), every leg of the
     default line runs its halo self-check, and the line carries the `rccl` object."""
-    line = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "20", "--no-cpu-baseline", "--spinup-ms", "20"],
+    line = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "20", "--full", "--no-cpu-baseline", "--spinup-ms", "20"],
                       {"QDSP_BENCH_REHEARSE": "1"})
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1 and line["scaling"] == "weak"
     assert line["config"]["halo_samples"] == 255 and line["config"]["samples_per_gpu_per_step"] == 1 << 20
@@ -259,7 +259,7 @@ def test_bench_two_ranks_rehearsal_end_to_end():
 def test_bench_self_ring_reports_the_communicator():
     """One rank as its own ring neighbour over REAL RCCL, through bench.py: the `rccl` object is filled from the communicator
     (ncclCommCount == 1 here; == N on an N-GPU run) and the exchange is timed on the ring's stream."""
-    line = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--log2n", "20", "--no-cpu-baseline", "--no-block-call", "--no-channelizer",
+    line = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--log2n", "20", "--full", "--no-cpu-baseline", "--no-block-call", "--no-channelizer",
                        "--spinup-ms", "20"], {"QDSP_BENCH_SELF_RING": "1"})
     rc = line["rccl"]
     assert rc["ring_transport"].startswith("qdsp_hip_ring")
