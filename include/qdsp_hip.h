@@ -80,7 +80,7 @@ int qdsp_hip_reload_env(void);
 int qdsp_hip_event_create(int device, void** ev);
 int qdsp_hip_event_destroy(void* ev);
 int qdsp_hip_event_wait(void* ev);
-int qdsp_hip_set_done_event(void* handle, void* ev);   /* any FIR / resampler / mixer / VFO / sine handle */
+int qdsp_hip_set_done_event(void* handle, void* ev);   /* any FIR / resampler / mixer / VFO / sine / demodulator handle */
 
 /* ---- memory helpers (for hosts that do not link the HIP runtime themselves) ----------- */
 /* Pinned host memory: replaces volk_malloc for stream buffers (src/dsp/stream.h:25-26) so
@@ -348,6 +348,50 @@ int qdsp_hip_math_process_ex(void* h, const void* a, int a_dev, const void* b, i
 int qdsp_hip_math_process_dev(void* h, const void* d_a, const void* d_b, int64_t count, void* d_out,
                               void* hip_stream);
 void qdsp_hip_math_destroy(void* h);
+
+/* ---- demodulators : src/dsp/demodulator.h ------------------------------------------------ */
+/* The data-parallel ones; what follows a VFO or a channelizer channel.  Output per input sample: one float (FM, AM), or a
+ * stereo_t {l, r} with l == r (FM_STEREO).
+ *   FM   cp[i] = fast_arctan2(im, re) (demodulator.h:14-30); d = cp[i] - cp[i-1], wrapped once by +-2 pi (with the float
+ *        literal 3.1415926535f); out = d / phasorSpeed, phasorSpeed = (2 * FL_M_PI) / (sampleRate / deviation) in float.
+ *        cp[-1] is the last phase of the previous call, 0 after create / reset; it stays on the device (no call waits for
+ *        it).  Bit-identical to the reference loop (demodulator.h:86-95), call boundaries included.
+ *   AM   out = |x| - avg (demodulator.h:353-372), |x| = sqrtf(re*re + im*im) bit-identical to VOLK's generic magnitude;
+ *        avg = the mean of THIS call's |x| (per channel), summed in FP64 in a fixed order and rounded once to float: within
+ *        an ulp of the exact mean, where the reference's float accumulator may be off by more.
+ * nchan channels are processed by one launch: channel-major rows, `in_stride` / `out_stride` samples apart (the layout
+ * qdsp_hip_chan_cf32_process_dev writes), each with its own carried phase and phasorSpeed.  process / process_ex (nchan 1):
+ * host pointers / link codes as for every *_process_ex, `count` <= max_block where a side is on the host (else
+ * QDSP_HIP_ESIZE).  process_dev: the nchan rows back to back (strides = count).  Device pointers: input 8-byte, output
+ * 4-byte (FM_STEREO: 8-byte) aligned; 16-byte aligned rows take the vector loads.  set_fm before the first call (default:
+ * sample_rate = deviation = 1); `chan` -1 = every channel.  get_phase synchronises the device. */
+#define QDSP_HIP_DEMOD_FM 0          /* FloatFMDemod :33-108 */
+#define QDSP_HIP_DEMOD_FM_STEREO 1   /* FMDemod :110-187     */
+#define QDSP_HIP_DEMOD_AM 2          /* AMDemod :332-378     */
+int qdsp_hip_demod_create(void** h, int device, int kind, int nchan, int max_block);
+int qdsp_hip_demod_set_fm(void* h, int chan, float sample_rate, float deviation);
+int qdsp_hip_demod_process(void* h, const float* in_iq, int count, void* out);
+int qdsp_hip_demod_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_demod_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_demod_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                     int64_t out_stride, void* hip_stream);
+int qdsp_hip_demod_get_phase(void* h, int chan, float* phase);
+int qdsp_hip_demod_set_phase(void* h, int chan, float phase);
+int qdsp_hip_demod_reset(void* h);
+void qdsp_hip_demod_destroy(void* h);
+/* SSBDemod :380-497: xlate_cf32's NCO (the same 64-bit phase and VOLK gain emulation, so the same deviation from the
+ * recursive phasor), only the real part stored.  phase_inc = (cos, sin)(+-(bandWidth / sampleRate) * FL_M_PI) for USB / LSB,
+ * (1, 0) for DSB, as SSBDemod::init computes it.  One channel; the entry points are those of xlate_cf32. */
+int qdsp_hip_ssb_cf32_create(void** h, int device, float phase_inc_re, float phase_inc_im, int max_block);
+int qdsp_hip_ssb_cf32_process(void* h, const float* in_iq, int count, float* out);
+int qdsp_hip_ssb_cf32_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_ssb_cf32_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_ssb_cf32_set_phase_inc(void* h, float phase_inc_re, float phase_inc_im);
+int qdsp_hip_ssb_cf32_get_phase(void* h, float* phase_re, float* phase_im);
+int qdsp_hip_ssb_cf32_set_phase(void* h, float phase_re, float phase_im);
+int qdsp_hip_ssb_cf32_advance(void* h, int64_t nsamples);
+int qdsp_hip_ssb_cf32_set_volk_gain(void* h, int on);
+void qdsp_hip_ssb_cf32_destroy(void* h);
 
 /* ---- synthetic IQ source (measurement harness) ------------------------------ */
 /* Counter-based uniform [-1,1) per float component, generated on device so benchmarks are

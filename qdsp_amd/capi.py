@@ -162,6 +162,31 @@ def load():
     sig("qdsp_hip_math_process_ex", i32, vp, vp, i32, vp, i32, i32, vp, i32)
     sig("qdsp_hip_math_process_dev", i32, vp, vp, vp, i64, vp, vp)
     sig("qdsp_hip_math_destroy", None, vp)
+    p = "qdsp_hip_demod"
+    sig(p + "_create", i32, pvp, i32, i32, i32, i32)
+    sig(p + "_set_fm", i32, vp, i32, C.c_float, C.c_float)
+    sig(p + "_process", i32, vp, vp, i32, vp)
+    sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+    sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp)
+    sig(p + "_get_phase", i32, vp, i32, fp)
+    sig(p + "_set_phase", i32, vp, i32, C.c_float)
+    sig(p + "_reset", i32, vp)
+    sig(p + "_destroy", None, vp)
+    p = "qdsp_hip_ssb_cf32"
+    sig(p + "_create", i32, pvp, i32, C.c_float, C.c_float, i32)
+    sig(p + "_process", i32, vp, vp, i32, vp)
+    sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+    sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+    sig(p + "_set_phase_inc", i32, vp, C.c_float, C.c_float)
+    sig(p + "_get_phase", i32, vp, fp, fp)
+    sig(p + "_set_phase", i32, vp, C.c_float, C.c_float)
+    sig(p + "_advance", i32, vp, i64)
+    sig(p + "_set_volk_gain", i32, vp, i32)
+    sig(p + "_destroy", None, vp)
+    sig("qdsp_hip_set_done_event", i32, vp, vp)
+    sig("qdsp_hip_event_create", i32, i32, pvp)
+    sig("qdsp_hip_event_destroy", i32, vp)
     sig("qdsp_hip_synth_iq_dev", i32, i32, vp, i64, i64, C.c_uint32, vp)
     sig("qdsp_hip_last_kernel", i32, vp, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32))
     sig("qdsp_hip_time_process_dev", i32, vp, vp, i64, vp, vp, i32, fp)

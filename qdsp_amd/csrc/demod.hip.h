@@ -1,0 +1,76 @@
+// demod.hip.h -- the demodulators of src/dsp/demodulator.h that are data-parallel (gfx950):
+//   fm_demod_kernel       FloatFMDemod / FMDemod (demodulator.h:33-187): fast_arctan2 of every sample, the difference to the
+//                         previous sample's phase wrapped once by +-2 pi, divided by phasorSpeed.  Bit-identical to the reference
+//                         loop, call boundaries included: the last sample's phase is carried on the device.
+//   am_partial_kernel     AMDemod (demodulator.h:353-372): |x| (VOLK's generic magnitude, separately rounded) summed in FP64,
+//   am_sub_kernel         one partial per workgroup; then every workgroup reduces its channel's partials in the same fixed
+//                         order, avg = (float)(sum / count), and stores |x| - avg.  Deterministic; no atomics, no grid barrier.
+//   ssb_demod_kernel      SSBDemod (demodulator.h:467-476): xlate_kernel's NCO, only the real part stored.
+// Every kernel takes `nchan` channel-major rows (grid.y = channel) with strides in samples: the layout
+// qdsp_hip_chan_cf32_process_dev writes.  The host side (handles, C entry points) is demod.hip.
+#pragma once
+#include "engine.hip.h"
+
+namespace qk {
+
+constexpr int kDemodNT = 256;     // lanes per workgroup
+constexpr int kDemodSpl = 8;      // consecutive samples per lane (four 16-byte loads)
+constexpr int kAmMaxParts = 1024; // workgroups (= FP64 partials) per channel of the AM passes
+
+struct FmArgs {
+    const float2* in;
+    void* out;                  // float, or float2 {l, r} (STEREO)
+    const float* phase;         // [nchan] phase carried from the previous call (slot cur)
+    float* phase_next;          // [nchan] this call's last phase (slot cur ^ 1)
+    const float* speed;         // [nchan] phasorSpeed
+    long long count, in_stride, out_stride;
+    int vec;                    // 1: every row 16-byte aligned
+};
+
+struct AmArgs {
+    const float2* in;
+    float* out;
+    double* part;               // [nchan][G]
+    long long count, in_stride, out_stride;
+    int G;                      // workgroups per channel
+    int vec;
+};
+
+}  // namespace qk
+
+namespace qh {
+
+// the demodulator handle (FM, FM stereo, AM, and SSB around an xlator engine); misc_ops.hip's harness helpers take it too
+constexpr uint32_t kDemodMagic = 0x51444d44u;  // "QDMD"
+constexpr int kDemodSsb = 3;                   // (QDSP_HIP_DEMOD_FM / _FM_STEREO / _AM are 0..2)
+constexpr int kDemodMaxChan = 65535;           // grid.y
+struct Demod {
+    uint32_t magic = kDemodMagic;
+    int device = 0;
+    int kind = 0;
+    int nchan = 1;
+    hipStream_t stream = nullptr;          // host-pointer path
+    hipStream_t last_stream = nullptr;     // process_ex: the stream of the previous call
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
+    void* d_in = nullptr;
+    void* d_out = nullptr;
+    int max_block = 0;
+    // FM: carried phase, double-buffered (lanes of one launch read slot cur, the last sample's lane writes cur ^ 1)
+    float* d_phase[2] = {nullptr, nullptr};
+    int cur = 0;
+    float* d_speed = nullptr;
+    std::vector<float> rate, dev, speed;
+    // AM: FP64 partials
+    double* d_part = nullptr;
+    // SSB: the NCO state of an xlate_cf32 engine (never launched through the engine itself)
+    Engine* nco = nullptr;
+    Launch last;
+};
+inline Demod* as_demod(void* h) {
+    Demod* d = static_cast<Demod*>(h);
+    return (d && d->magic == kDemodMagic) ? d : nullptr;
+}
+int demod_time(Demod* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
+
+}  // namespace qh

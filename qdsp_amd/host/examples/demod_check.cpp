@@ -1,0 +1,136 @@
+// demod_check -- source -> VFO -> demodulator -> sink graphs of the C++ block mirror (qdsp_amd/host/dsp/demodulator.h), for
+// the tests to compare with the restatement of src/dsp/demodulator.h applied to the VFO's own output.  A harness, not part of
+// the product.
+//
+//   demod_check vfo <in.cf32> <out.cf32> <block> <offset> <inSR> <outSR> <bw>
+//                   source -> VFO -> sink: what the demodulators below read
+//   demod_check fm|fms|am|ssb <dev|host> <in.cf32> <out> <block> <offset> <inSR> <outSR> <bw> [<p1> [<p2>]]
+//                   source -> VFO -> FloatFMDemod (fm, p1 = deviation) | FMDemod (fms: stereo_t out) | AMDemod (am) |
+//                   SSBDemod (ssb, p1 = bandWidth, p2 = mode 0 USB / 1 LSB / 2 DSB) -> sink, at sample rate outSR.
+//                   dev: the VFO hands its blocks to the demodulator in device memory (the links the blocks set up
+//                   themselves); host: the same graph with that link moved to the host buffers.
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include <dsp/demodulator.h>
+#include <dsp/sink.h>
+#include <dsp/source.h>
+#include <dsp/vfo.h>
+
+using namespace dsp;
+
+static std::vector<complex_t> readAll(const char* path) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); exit(2); }
+    const size_t bytes = (size_t)f.tellg();
+    f.seekg(0);
+    std::vector<complex_t> v(bytes / sizeof(complex_t));
+    f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(complex_t)));
+    return v;
+}
+
+struct Feed {
+    std::vector<complex_t> data;
+    size_t pos = 0;
+    int block = 1;
+    static int pull(complex_t* dst, void* ctx) {
+        Feed* f = static_cast<Feed*>(ctx);
+        if (f->pos >= f->data.size()) { return -1; }
+        const size_t n = std::min<size_t>((size_t)f->block, f->data.size() - f->pos);
+        memcpy(dst, f->data.data() + f->pos, n * sizeof(complex_t));
+        f->pos += n;
+        return (int)n;
+    }
+};
+
+// a file sink that counts the blocks it has written
+template <class T> struct Writer {
+    std::ofstream file;
+    std::atomic<long> blocks{0};
+    std::atomic<long> samples{0};
+    static void push(T* src, int count, void* ctx) {
+        Writer* w = static_cast<Writer*>(ctx);
+        w->file.write(reinterpret_cast<const char*>(src), (std::streamsize)count * sizeof(T));
+        w->samples += count;
+        w->blocks++;
+    }
+};
+
+// source -> VFO -> [BLOCK] -> sink; waits until every input block has come out the far end
+template <class T, class MAKE>
+static int runGraph(const char* inPath, const char* outPath, int block, float off, float inSR, float outSR, float bw, bool hostLink,
+                    MAKE make) {
+    Feed feed;
+    feed.data = readAll(inPath);
+    feed.block = block;
+    const long nblocks = (long)((feed.data.size() + block - 1) / block);
+    HandlerSource<complex_t> src(Feed::pull, &feed);
+    VFO vfo(&src.out, off, inSR, outSR, bw);
+    generic_unnamed_block* blk = nullptr;
+    stream<T>* last = make(vfo.out, blk);
+    if (hostLink) { vfo.out->releaseConsumer(); }   // the VFO writes its host buffers, the demodulator uploads them
+    Writer<T> w;
+    w.file.open(outPath, std::ios::binary);
+    HandlerSink<T> sink(last, Writer<T>::push, &w);
+    sink.start();
+    if (blk) { blk->start(); }
+    vfo.start();
+    src.start();
+    const auto t0 = std::chrono::steady_clock::now();
+    while (w.blocks.load() < nblocks) {
+        std::this_thread::sleep_for(std::chrono::milliseconds(1));
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) { fprintf(stderr, "graph timed out\n"); return 3; }
+        if (hipBlockErrors() > 0) { fprintf(stderr, "a block failed\n"); return 4; }
+    }
+    src.stop();
+    vfo.stop();
+    if (blk) { blk->stop(); }
+    sink.stop();
+    delete blk;
+    w.file.close();
+    printf("graph ok: %zu in, %ld out, %ld blocks, %s link\n", feed.data.size(), w.samples.load(), nblocks, hostLink ? "host" : "device");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 2) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
+    const std::string mode = argv[1];
+    if (mode == "vfo" && argc >= 9) {
+        const float off = (float)atof(argv[5]), inSR = (float)atof(argv[6]), outSR = (float)atof(argv[7]), bw = (float)atof(argv[8]);
+        return runGraph<complex_t>(argv[2], argv[3], atoi(argv[4]), off, inSR, outSR, bw, false,
+                                   [](stream<complex_t>* s, generic_unnamed_block*&) { return s; });
+    }
+    if (argc < 10) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
+    const std::string link = argv[2];
+    if (link != "dev" && link != "host") { fprintf(stderr, "link: dev | host\n"); return 2; }
+    const bool hostLink = link == "host";
+    const char* in = argv[3];
+    const char* out = argv[4];
+    const int block = atoi(argv[5]);
+    const float off = (float)atof(argv[6]), inSR = (float)atof(argv[7]), outSR = (float)atof(argv[8]), bw = (float)atof(argv[9]);
+    const float p1 = argc > 10 ? (float)atof(argv[10]) : 0.0f;
+    const int p2 = argc > 11 ? atoi(argv[11]) : 0;
+    // the demodulator block and its output stream
+    auto with = [](auto* d, generic_unnamed_block*& blk) { blk = d; return &d->out; };
+    if (mode == "fm")
+        return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
+                               [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new FloatFMDemod(s, outSR, p1), b); });
+    if (mode == "fms")
+        return runGraph<stereo_t>(in, out, block, off, inSR, outSR, bw, hostLink,
+                                  [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new FMDemod(s, outSR, p1), b); });
+    if (mode == "am")
+        return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
+                               [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new AMDemod(s), b); });
+    if (mode == "ssb")
+        return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
+                               [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new SSBDemod(s, outSR, p1, p2), b); });
+    fprintf(stderr, "unknown mode %s\n", mode.c_str());
+    return 2;
+}

@@ -446,3 +446,133 @@ class Math:
         capi.check(self._L.qdsp_hip_math_process(self._h, x.ctypes.data, y.ctypes.data, x.size, o.ctypes.data), "qdsp_hip_math_process")
         return o
 
+
+
+class _Demod(_Op):
+    """Complex in, real out (one float per sample, or a stereo_t {l, r} pair: `_stereo`).  numpy input: the host entry
+    point (one channel); a 1-D torch tensor: *_process_dev; a 2-D one: one row per channel (`process_batch`)."""
+
+    _stereo = False
+    nchan = 1
+
+    def _out_shape(self, *lead):
+        return (*lead, 2) if self._stereo else tuple(lead)
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=np.complex64)
+        y = np.empty(self._out_shape(max(a.size, 1)), dtype=np.float32)
+        capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:a.size]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.complex64
+        n = x.numel() // self.nchan
+        if out is None:
+            out = torch.empty(self._out_shape(max(x.numel(), 1)), dtype=torch.float32, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= x.numel()
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
+        return out[:x.numel()]
+
+    def process_batch(self, x, out=None, count: int = None):
+        """Channel c = row c of the 2-D complex64 tensor `x` (rows may be padded: x.stride(0) >= count, e.g. the
+        Channelizer's output, or a slice of it).  Returns (nchan, count) float32 (stereo: (nchan, count, 2))."""
+        import torch
+
+        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.complex64 and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        if out is None:
+            out = torch.empty(self._out_shape(self.nchan, max(n, 1)), dtype=torch.float32, device=x.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == (2 if self._stereo else 1)
+        out_stride = out.stride(0) // (2 if self._stereo else 1)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._L.qdsp_hip_demod_process_batch_dev(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out_stride, stream),
+                   "qdsp_hip_demod_process_batch_dev")
+        return out[:, :n]
+
+    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
+        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
+        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
+
+    def set_done_event(self, ev: int):
+        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
+
+
+class FmDemod(_Demod):
+    """FloatFMDemod (stereo=False, float out) / FMDemod (stereo=True, {l, r} with l == r) of src/dsp/demodulator.h:33-187,
+    bit-identical to the reference loop; `nchan` channels per launch, each with its own deviation and carried phase."""
+
+    _prefix = "qdsp_hip_demod"
+
+    def __init__(self, sample_rate, deviation, stereo: bool = False, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self._stereo = bool(stereo)
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, 1 if stereo else 0, self.nchan, max_block), "qdsp_hip_demod_create")
+        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
+        devs = np.broadcast_to(np.asarray(deviation, dtype=np.float32), (self.nchan,))
+        for c in range(self.nchan):
+            self.set_fm(float(rates[c]), float(devs[c]), c)
+
+    def set_fm(self, sample_rate: float, deviation: float, chan: int = -1):
+        capi.check(self._fn("set_fm")(self._h, int(chan), sample_rate, deviation), "qdsp_hip_demod_set_fm")
+
+    def get_phase(self, chan: int = 0) -> float:
+        v = C.c_float()
+        capi.check(self._fn("get_phase")(self._h, int(chan), C.byref(v)))
+        return np.float32(v.value)
+
+    def set_phase(self, phase: float, chan: int = -1):
+        capi.check(self._fn("set_phase")(self._h, int(chan), phase))
+
+    def reset(self):
+        capi.check(self._fn("reset")(self._h))
+
+
+class AmDemod(_Demod):
+    """AMDemod (src/dsp/demodulator.h:332-378): |x| minus the mean of the call's |x|, per channel."""
+
+    _prefix = "qdsp_hip_demod"
+
+    def __init__(self, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, 2, self.nchan, max_block), "qdsp_hip_demod_create")
+
+
+def ssb_phase_delta(sample_rate: float, bandwidth: float, mode: int):
+    """phaseDelta exactly as SSBDemod::init computes it (demodulator.h:408-419): float operands, the float cos/sin."""
+    theta = np.float32(np.float32(bandwidth) / np.float32(sample_rate)) * FL_M_PI
+    if mode == SsbDemod.DSB:
+        return 1.0, 0.0
+    if mode == SsbDemod.LSB:
+        theta = np.float32(-np.float32(np.float32(bandwidth) / np.float32(sample_rate))) * FL_M_PI
+    elif mode != SsbDemod.USB:
+        raise ValueError(f"mode {mode}")
+    return float(_libm().cosf(C.c_float(theta))), float(_libm().sinf(C.c_float(theta)))
+
+
+class SsbDemod(_Demod, _NcoMixin):
+    """SSBDemod (src/dsp/demodulator.h:380-497): the xlator's NCO, real part out."""
+
+    USB, LSB, DSB = 0, 1, 2
+    _prefix = "qdsp_hip_ssb_cf32"
+
+    def __init__(self, sample_rate: float = None, bandwidth: float = None, mode: int = 0, phase_inc=None, device: int = 0,
+                 max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        re, im = phase_inc if phase_inc is not None else ssb_phase_delta(sample_rate, bandwidth, mode)
+        self.phase_inc = (re, im)
+        capi.check(self._fn("create")(C.byref(self._h), device, re, im, max_block), "qdsp_hip_ssb_cf32_create")
+
+
+__all__ += ["FmDemod", "AmDemod", "SsbDemod", "ssb_phase_delta"]
