@@ -96,7 +96,9 @@ __device__ __forceinline__ float2 load_stream(const float2* p) {
 // sums wait in a wave-private LDS patch (no register for them in the rounds), then take the same inverse.
 //
 // RD (round 4): REAL data -- PolyphaseResampler<float> with interp 1, decimation 8 / 4.  A real filter is linear over the reals, so TWO segments of the
-// real stream ride one set of complex transforms as re / im: pair p = segments (p, p + ceil(nseg / 2)); the loads are two 4-byte loads per row element,
+// real stream ride one set of complex transforms as re / im: pair p = ADJACENT segments (2p, 2p + 1), as the other real forms pair them.  The transforms
+// mix re and im (exactly in the twiddle products, completely for a NaN / Inf), so a pair's members must be neighbours in the stream: pairing p with
+// p + ceil(nseg / 2) (round 4) carried a bad sample -- and a loud segment's FP32 error floor -- half a call away.  The loads are two 4-byte loads per row element,
 // the stores two 4-byte stores (each stream's own bounds); everything between is the complex kernel.  in / out / hist are float arrays.
 template <bool ROT, int PH, bool RD = false>
 __device__ __forceinline__ void pfb_body(const PfbArgs& a) {
@@ -210,12 +212,12 @@ __device__ __forceinline__ void pfb_body(const PfbArgs& a) {
     };
     float2 v[64];
     const float* __restrict__ inr = reinterpret_cast<const float*>(a.in);        // RD: the real stream
-    const int nhalf = (a.nseg + 1) >> 1;                                          // RD: pairs; segment b rides with segment b + nhalf
-    const int nloop = RD ? nhalf : a.nseg;
-    auto segB_of = [&](int b) { return b + nhalf < a.nseg ? b + nhalf : b; };     // (an odd count: the last pair's second member repeats the first, not stored)
+    const int nloop = RD ? (a.nseg + 1) >> 1 : a.nseg;                           // RD: pairs; pair p = segments 2p, 2p + 1
+    auto segA_of = [&](int b) { return RD ? 2 * b : b; };
+    auto segB_of = [&](int b) { return 2 * b + 1 < a.nseg ? 2 * b + 1 : 2 * b; };  // (an odd count: the last pair's second member repeats the first, not stored)
     if constexpr (RD) {
         const int b0 = wave0 < nloop ? wave0 : 0;
-        const float* __restrict__ pa = inr + clamped(seg_start(b0)) + l;
+        const float* __restrict__ pa = inr + clamped(seg_start(segA_of(b0))) + l;
         const float* __restrict__ pb2 = inr + clamped(seg_start(segB_of(b0))) + l;
 #pragma unroll
         for (int r = 0; r < 64; r++) v[r] = make_float2(pa[64 * r], pb2[64 * r]);
@@ -226,7 +228,8 @@ __device__ __forceinline__ void pfb_body(const PfbArgs& a) {
     }
 #pragma unroll 1
     for (int b = wave0; b < nloop; b += nwaves) {
-        const long long S0 = seg_start(b);
+        const int bA = segA_of(b);                                                // (the segment; b counts pairs with real data)
+        const long long S0 = seg_start(bA);
         const int bB = RD ? segB_of(b) : b;
         const long long S0B = seg_start(bB);
         // ---- v[8 j + q'] = seg[512 j + 64 q' + l] (whole 512-byte rows), already requested ---------------------
@@ -275,8 +278,8 @@ __device__ __forceinline__ void pfb_body(const PfbArgs& a) {
         // RD: ONE per-lane pointer (stream A) through the rounds; stream B's is rebuilt in each round from the wave-uniform distance between the two
         // segments (two pointers held across the rounds cost the two-phase body its last two registers; bases in SGPRs with a 32-bit lane offset
         // -- the other way to save them -- run 40 % slower: 95 against 67 us per 2^26 samples at decimation 8)
-        const float* __restrict__ pnA = inr + clamped(seg_start(bn)) + l;
-        const long long dAB64 = clamped(seg_start(RD ? segB_of(bn) : bn)) - clamped(seg_start(bn));
+        const float* __restrict__ pnA = inr + clamped(seg_start(segA_of(bn))) + l;
+        const long long dAB64 = clamped(seg_start(RD ? segB_of(bn) : bn)) - clamped(seg_start(segA_of(bn)));   // (8 Lo but at the ends of the call)
         unsigned dABlo = __builtin_amdgcn_readfirstlane((unsigned)dAB64), dABhi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)dAB64 >> 32));
         float2 vn[64];
         // ---- forward, column index a = 64 j + 8 q' + g', bin k = k0 + 8 kq + 64 kg ----------------------------
@@ -405,7 +408,7 @@ __device__ __forceinline__ void pfb_body(const PfbArgs& a) {
             pb = dcmul(pb, a.rot_step);
         }
         // (32-bit lane offsets from a segment base: per-lane 64-bit output indices get hoisted out of the segment loop and spilled)
-        const long long base = PH * ((long long)b * a.Lo - (a.Q - 1));           // output index of element a' = 0, phase 0
+        const long long base = PH * ((long long)bA * a.Lo - (a.Q - 1));           // output index of element a' = 0, phase 0
         const long long room = a.nout - base;
         const int hi = room > 8192 ? 8192 : (int)room;                            // offsets below this one are inside the call
         const int lo = base > 0 ? -8 : (int)-base;                                // ... and from this one on not before its start
@@ -413,7 +416,7 @@ __device__ __forceinline__ void pfb_body(const PfbArgs& a) {
         // RD: the second member of the pair has its own output window
         const long long baseB = PH * ((long long)bB * a.Lo - (a.Q - 1));
         const long long roomB = a.nout - baseB;
-        const bool haveB = RD && bB != b;                                                // (a repeated segment stores nothing)
+        const bool haveB = RD && bB != bA;                                               // (a repeated segment stores nothing)
         const int hiB = haveB ? (roomB > 8192 ? 8192 : (int)roomB) : 0;
         const int loB = haveB ? (baseB > 0 ? -8 : (int)-baseB) : 0;
         float* __restrict__ orA = reinterpret_cast<float*>(a.out) + base;

@@ -403,7 +403,7 @@ def test_decimate_by_two_both_overlap_save_forms(ops, monkeypatch, ntaps, rot):
 @pytest.mark.parametrize("dec", [8, 4])
 def test_polyphase_overlap_save_decimator_real_data(ops, monkeypatch, ntaps, dec):
     """pfb_dec8_real_kernel / pfb_dec4_real_kernel (round 4): PolyphaseResampler<float> at decimation 8 / 4 -- TWO segments of the real stream ride
-    one set of complex transforms as re / im (pair p = segments p and p + ceil(nseg / 2)).  Ragged calls: an odd and an even number of segments, a call of exactly
+    one set of complex transforms as re / im (pair p = adjacent segments 2p and 2p + 1).  Ragged calls: an odd and an even number of segments, a call of exactly
     one segment (its partner repeats it and stores nothing), pairs whose members read the history / are zero-filled at the end, a call below
     one segment (another kernel), the history handed on; against the FP64 oracle and against the 4096-point kernel on the same stream."""
     import torch
