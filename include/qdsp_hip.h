@@ -393,6 +393,41 @@ int qdsp_hip_ssb_cf32_advance(void* h, int64_t nsamples);
 int qdsp_hip_ssb_cf32_set_volk_gain(void* h, int on);
 void qdsp_hip_ssb_cf32_destroy(void* h);
 
+/* ---- de-emphasis : BFMDeemp, src/dsp/filter.h:90-173 -------------------------------------- */
+/* y[i] = alpha x[i] + (1 - alpha) y[i-1], alpha = dt / (tau + dt), dt = 1.0f / sampleRate, all coefficients in float as the
+ * reference computes them.  The recurrence is evaluated as a parallel prefix scan of affine maps composed in FP64, every
+ * output rounded to float once: not the bits of the reference's float loop (no reassociated scan can give those), but within
+ * 0.5 ulp + 2^-40 * (the same filter run over |x|) of the exact recurrence, and no further from it than the float loop is.
+ * Rows are float (MONO) or stereo_t {l, r} (STEREO; l and r filtered independently with the same alpha): nchan channel-major
+ * rows, strides in samples, the layout qdsp_hip_demod_process_batch_dev writes; each channel has its own alpha and state.
+ * State: y[-1] of the next call, kept on the device in FP64 per channel and component; 0 after create / reset.  get_state
+ * rounds it to float (= the last output) and synchronises the device; set_state widens a float.  At the start of a call a
+ * state that is not finite reads as 0.  For NaN that is the reference's rule (filter.h:140-145): a NaN input poisons its
+ * own component from that sample to the end of the call, the next call starts clean.  For +-Inf it is a deliberate departure:
+ * the reference's state would stay Inf for ever; here the outputs from an Inf input to the end of that call are not finite
+ * (Inf or NaN, unspecified) and the next call starts from 0.
+ * set_bypass(1): process* copies input to output and leaves the state alone (BFMDeemp::bypass).  set before the first call
+ * (default: sample_rate 1, tau 0, i.e. alpha 1, y = x); `chan` -1 = every channel.  count == 0 is a no-op.
+ * process / process_ex (nchan 1): host pointers / link codes as for every *_process_ex, `count` <= max_block where a side is
+ * on the host (else QDSP_HIP_ESIZE).  process_dev: the nchan rows back to back (strides = count).  Device pointers: 4-byte
+ * (STEREO: 8-byte) aligned; 16-byte aligned rows take the vector loads and stores.  In place (d_out == d_in, with
+ * out_stride == in_stride) is supported and gives the same bits; any other overlap of input and output is not. */
+#define QDSP_HIP_DEEMP_MONO   0   /* float rows    */
+#define QDSP_HIP_DEEMP_STEREO 1   /* stereo_t rows */
+int qdsp_hip_deemp_create(void** h, int device, int kind, int nchan, int max_block);
+int qdsp_hip_deemp_set(void* h, int chan, float sample_rate, float tau);
+int qdsp_hip_deemp_set_bypass(void* h, int on);
+int qdsp_hip_deemp_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_deemp_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_deemp_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_deemp_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                     int64_t out_stride, void* hip_stream);
+int qdsp_hip_deemp_get_state(void* h, int chan, float* l, float* r);   /* MONO: r may be NULL */
+int qdsp_hip_deemp_set_state(void* h, int chan, float l, float r);
+int qdsp_hip_deemp_get_alpha(void* h, int chan, float* alpha);
+int qdsp_hip_deemp_reset(void* h);
+void qdsp_hip_deemp_destroy(void* h);
+
 /* ---- synthetic IQ source (measurement harness) ------------------------------ */
 /* Counter-based uniform [-1,1) per float component, generated on device so benchmarks are
  * HBM->HBM.  Bit-identical to oracle_synth_iq() for the same (first_sample, seed). */

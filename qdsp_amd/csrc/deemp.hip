@@ -1,0 +1,452 @@
+// deemp.hip -- BFMDeemp as a batched FP64 prefix scan (design notes: deemp.hip.h) and its C entry points.
+#include "deemp.hip.h"
+
+namespace qk {
+
+namespace {
+// y -> A y + B[c]; both components of a stereo_t share the coefficient, hence one A
+template <int NC> struct Aff {
+    double A;
+    double B[NC];
+};
+
+template <int NC> __device__ __forceinline__ Aff<NC> aff_identity() {
+    Aff<NC> r;
+    r.A = 1.0;
+#pragma unroll
+    for (int c = 0; c < NC; c++) r.B[c] = 0.0;
+    return r;
+}
+
+// `later` after `earlier`
+template <int NC> __device__ __forceinline__ Aff<NC> compose(const Aff<NC>& later, const Aff<NC>& earlier) {
+    Aff<NC> r;
+    r.A = later.A * earlier.A;
+#pragma unroll
+    for (int c = 0; c < NC; c++) r.B[c] = fma(later.A, earlier.B[c], later.B[c]);
+    return r;
+}
+
+template <int NC> __device__ __forceinline__ Aff<NC> shfl_up(const Aff<NC>& v, int d) {
+    Aff<NC> r;
+    r.A = __shfl_up(v.A, d);
+#pragma unroll
+    for (int c = 0; c < NC; c++) r.B[c] = __shfl_up(v.B[c], d);
+    return r;
+}
+
+// the up to kDemodSpl samples at row[i0..) (NC floats each): 16-byte loads when the row is aligned and the lane's samples are all there
+template <int NC> __device__ __forceinline__ int load_lane(const float* row, long long i0, long long count, int vec, float (&x)[kDemodSpl * NC]) {
+    const long long rem = count - i0;
+    const int n = rem < 0 ? 0 : (rem < kDemodSpl ? (int)rem : kDemodSpl);
+    if (vec && n == kDemodSpl) {
+        const float4* p = reinterpret_cast<const float4*>(row + i0 * NC);
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC / 4; j++) {
+            const float4 v = p[j];
+            x[4 * j] = v.x;
+            x[4 * j + 1] = v.y;
+            x[4 * j + 2] = v.z;
+            x[4 * j + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC; j++) x[j] = (j < n * NC) ? row[i0 * NC + j] : 0.0f;
+    }
+    return n;
+}
+
+template <int NC> __device__ __forceinline__ void store_lane(float* row, long long i0, int n, int vec, const float (&y)[kDemodSpl * NC]) {
+    if (vec && n == kDemodSpl) {
+        float4* q = reinterpret_cast<float4*>(row + i0 * NC);
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC / 4; j++) q[j] = make_float4(y[4 * j], y[4 * j + 1], y[4 * j + 2], y[4 * j + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC; j++)
+            if (j < n * NC) row[i0 * NC + j] = y[j];
+    }
+}
+
+// the lane's n samples as one map
+template <int NC> __device__ __forceinline__ Aff<NC> fold_lane(const float (&x)[kDemodSpl * NC], int n, double a, double b) {
+    Aff<NC> p = aff_identity<NC>();
+#pragma unroll
+    for (int j = 0; j < kDemodSpl; j++) {
+        if (j < n) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) p.B[c] = fma(b, p.B[c], a * (double)x[j * NC + c]);
+            p.A *= b;
+        }
+    }
+    return p;
+}
+
+// One tile: from every lane's own map, the map of all lanes before it (*ex) and of the whole tile (returned).  Hillis-Steele
+// over the 64 lanes of a wave by cross-lane moves, then the kDemodNT / 64 wave totals through `wt`; always the same tree.
+template <int NC> __device__ __forceinline__ Aff<NC> tile_scan(const Aff<NC>& p, Aff<NC>* wt, Aff<NC>* ex) {
+    constexpr int NW = kDemodNT / 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    Aff<NC> inc = p;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const Aff<NC> q = shfl_up(inc, d);
+        if (lane >= d) inc = compose(inc, q);
+    }
+    if (lane == 63) wt[w] = inc;
+    __syncthreads();
+    Aff<NC> e = shfl_up(inc, 1);
+    if (lane == 0) e = aff_identity<NC>();
+    Aff<NC> pre = aff_identity<NC>(), tot = aff_identity<NC>();
+#pragma unroll
+    for (int k = 0; k < NW; k++) {
+        const Aff<NC> t = wt[k];
+        if (k < w) pre = compose(t, pre);
+        tot = compose(t, tot);
+    }
+    *ex = compose(e, pre);
+    __syncthreads();   // (wt is written again by the next tile)
+    return tot;
+}
+
+// chunk g of row c: the carried state moved over the chunks before it, then tile by tile
+template <int NC> __device__ __forceinline__ void scan_chunk(const DeempArgs& a) {
+    __shared__ Aff<NC> wt[kDemodNT / 64];
+    const int c = blockIdx.y, g = blockIdx.x;
+    const float alpha = a.alpha[c];
+    const double al = (double)alpha, b = (double)(1.0f - alpha);
+    double carry[NC];
+#pragma unroll
+    for (int k = 0; k < NC; k++) {
+        const double s = a.state[c * NC + k];
+        carry[k] = isfinite(s) ? s : 0.0;
+    }
+    const double* part = a.part + (long long)c * a.G * (1 + NC);
+    for (int k = 0; k < g; k++) {
+#pragma unroll
+        for (int m = 0; m < NC; m++) carry[m] = fma(part[k * (1 + NC)], carry[m], part[k * (1 + NC) + 1 + m]);
+    }
+    const float* in = a.in + (long long)c * a.in_stride * NC;
+    float* out = a.out + (long long)c * a.out_stride * NC;
+    const long long tiles = (a.count + (long long)kDemodNT * kDemodSpl - 1) / ((long long)kDemodNT * kDemodSpl);
+    const long long t0 = (long long)g * a.T;
+    const long long t1 = t0 + a.T < tiles ? t0 + a.T : tiles;
+    for (long long t = t0; t < t1; t++) {
+        const long long i0 = (t * kDemodNT + threadIdx.x) * kDemodSpl;
+        float x[kDemodSpl * NC];
+        const int n = load_lane<NC>(in, i0, a.count, a.vec, x);
+        Aff<NC> ex;
+        const Aff<NC> tot = tile_scan(fold_lane<NC>(x, n, al, b), wt, &ex);
+        double y[NC];
+#pragma unroll
+        for (int m = 0; m < NC; m++) y[m] = fma(ex.A, carry[m], ex.B[m]);
+        float o[kDemodSpl * NC];
+#pragma unroll
+        for (int j = 0; j < kDemodSpl; j++) {
+#pragma unroll
+            for (int m = 0; m < NC; m++) {
+                if (j < n) y[m] = fma(b, y[m], al * (double)x[j * NC + m]);
+                o[j * NC + m] = (float)y[m];
+            }
+        }
+        store_lane<NC>(out, i0, n, a.vec, o);
+        if (n > 0 && i0 + n == a.count) {
+#pragma unroll
+            for (int m = 0; m < NC; m++) a.state_next[c * NC + m] = y[m];
+        }
+#pragma unroll
+        for (int m = 0; m < NC; m++) carry[m] = fma(tot.A, carry[m], tot.B[m]);
+    }
+}
+}  // namespace
+
+template <int NC> __global__ __launch_bounds__(kDemodNT) void deemp_row_kernel(const DeempArgs a) { scan_chunk<NC>(a); }
+template <int NC> __global__ __launch_bounds__(kDemodNT) void deemp_scan_kernel(const DeempArgs a) { scan_chunk<NC>(a); }
+
+// pass 1; grid (G - 1, nchan): every tile of these chunks is full
+template <int NC> __global__ __launch_bounds__(kDemodNT) void deemp_partial_kernel(const DeempArgs a) {
+    __shared__ Aff<NC> wt[kDemodNT / 64];
+    const int c = blockIdx.y, g = blockIdx.x;
+    const float alpha = a.alpha[c];
+    const double al = (double)alpha, b = (double)(1.0f - alpha);
+    const float* in = a.in + (long long)c * a.in_stride * NC;
+    Aff<NC> acc = aff_identity<NC>();
+    const long long t0 = (long long)g * a.T;
+    for (long long t = t0; t < t0 + a.T; t++) {
+        const long long i0 = (t * kDemodNT + threadIdx.x) * kDemodSpl;
+        float x[kDemodSpl * NC];
+        const int n = load_lane<NC>(in, i0, a.count, a.vec, x);
+        Aff<NC> ex;
+        acc = compose(tile_scan(fold_lane<NC>(x, n, al, b), wt, &ex), acc);
+    }
+    if (threadIdx.x == 0) {
+        double* p = a.part + ((long long)c * a.G + g) * (1 + NC);
+        p[0] = acc.A;
+#pragma unroll
+        for (int m = 0; m < NC; m++) p[1 + m] = acc.B[m];
+    }
+}
+
+}  // namespace qk
+
+namespace qh {
+
+namespace {
+int comps(const Deemp* d) { return d->kind == QDSP_HIP_DEEMP_STEREO ? 2 : 1; }
+bool chan_ok(const Deemp* d, int chan) { return chan >= 0 && chan < d->nchan; }
+
+void deemp_free(Deemp* d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    (void)hipDeviceSynchronize();
+    for (void* p : {d->d_in, d->d_out, (void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_alpha, (void*)d->d_part})
+        if (p) (void)hipFree(p);
+    if (d->ev0) (void)hipEventDestroy(d->ev0);
+    if (d->ev1) (void)hipEventDestroy(d->ev1);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    d->magic = 0;
+    delete d;
+}
+
+// d_in / d_out: nchan rows of `count` samples, in_stride / out_stride samples apart
+int deemp_launch(Deemp* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s) {
+    if (count < 0 || (count > 0 && (!d_in || !d_out))) return QDSP_HIP_EINVAL;
+    if (in_stride < count || out_stride < count) return QDSP_HIP_EINVAL;
+    const int nc = comps(d);
+    const uintptr_t amask = (uintptr_t)(nc * sizeof(float) - 1);
+    if (((uintptr_t)d_in & amask) || ((uintptr_t)d_out & amask)) return QDSP_HIP_EINVAL;
+    if (d_in == d_out && in_stride != out_stride) return QDSP_HIP_EINVAL;   // in place: the same rows exactly
+    if (count == 0) return 0;
+    HIPCHK(hipSetDevice(d->device));
+    const size_t es = (size_t)nc * sizeof(float);
+    if (d->bypass) {
+        if (d_in != d_out)
+            HIPCHK(hipMemcpy2DAsync(d_out, (size_t)out_stride * es, d_in, (size_t)in_stride * es, (size_t)count * es, (size_t)d->nchan,
+                                    hipMemcpyDeviceToDevice, s));
+        d->last = Launch{"bypass", 0, 0, 0};
+        return 0;
+    }
+    const long long per_wg = (long long)qk::kDemodNT * qk::kDemodSpl;
+    const long long tiles = (count + per_wg - 1) / per_wg;
+    qk::DeempArgs a;
+    a.in = static_cast<const float*>(d_in);
+    a.out = static_cast<float*>(d_out);
+    a.alpha = d->d_alpha;
+    a.state = d->d_state[d->cur];
+    a.state_next = d->d_state[d->cur ^ 1];
+    a.part = d->d_part;
+    a.count = count;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    const int per16 = 4 / nc;   // samples per 16 bytes
+    a.vec = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0 && in_stride % per16 == 0 && out_stride % per16 == 0;
+    const int lds = (int)((qk::kDemodNT / 64) * (1 + nc) * sizeof(double));
+    if (tiles <= qk::kDeempRowTiles) {
+        a.T = tiles;
+        a.G = 1;
+        const dim3 grid(1, (unsigned)d->nchan);
+        if (nc == 2) hipLaunchKernelGGL((qk::deemp_row_kernel<2>), grid, dim3(qk::kDemodNT), 0, s, a);
+        else hipLaunchKernelGGL((qk::deemp_row_kernel<1>), grid, dim3(qk::kDemodNT), 0, s, a);
+        HIPCHK(hipGetLastError());
+        d->last = Launch{"deemp_row_kernel", 1, qk::kDemodNT, lds};
+    } else {
+        const long long g0 = tiles < qk::kAmMaxParts ? tiles : qk::kAmMaxParts;
+        a.T = (tiles + g0 - 1) / g0;
+        a.G = (int)((tiles + a.T - 1) / a.T);   // >= 2: tiles > kDeempRowTiles
+        const dim3 g1((unsigned)(a.G - 1), (unsigned)d->nchan), g2((unsigned)a.G, (unsigned)d->nchan);
+        if (nc == 2) {
+            hipLaunchKernelGGL((qk::deemp_partial_kernel<2>), g1, dim3(qk::kDemodNT), 0, s, a);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL((qk::deemp_scan_kernel<2>), g2, dim3(qk::kDemodNT), 0, s, a);
+        } else {
+            hipLaunchKernelGGL((qk::deemp_partial_kernel<1>), g1, dim3(qk::kDemodNT), 0, s, a);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL((qk::deemp_scan_kernel<1>), g2, dim3(qk::kDemodNT), 0, s, a);
+        }
+        HIPCHK(hipGetLastError());
+        d->last = Launch{"deemp_scan_kernel", a.G, qk::kDemodNT, lds};
+    }
+    d->cur ^= 1;
+    return 0;
+}
+
+// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
+int deemp_process_ex(Deemp* d, const void* in, int in_link, int count, void* out, int out_link) {
+    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
+    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
+        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
+        return QDSP_HIP_EINVAL;
+    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
+    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
+    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
+    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
+    if (count == 0) return 0;
+    HIPCHK(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
+        st = shared_stream(d->device);
+        if (!st) return QDSP_HIP_ENOMEM;
+    }
+    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
+    d->last_stream = st;
+    const size_t bytes = (size_t)count * comps(d) * sizeof(float);
+    const void* src = in;
+    if (in_link == QDSP_HIP_LINK_HOST) {
+        HIPCHK(hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, st));
+        src = d->d_in;
+    }
+    int rc = deemp_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
+    if (rc) return rc;
+    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, bytes, hipMemcpyDeviceToHost, st));
+    if (deferred) {
+        HIPCHK(hipEventRecord(d->done_ev, st));
+        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
+        HIPCHK(hipEventSynchronize(d->done_ev));
+        return 0;
+    }
+    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
+        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
+    return 0;
+}
+}  // namespace
+
+int deemp_time(Deemp* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
+    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
+    HIPCHK(hipSetDevice(d->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(hipEventRecord(d->ev0, s));
+    for (int i = 0; i < iters; i++) {
+        const int rc = deemp_launch(d, d_in, count, count, d_out, count, s);
+        if (rc) return rc;
+    }
+    HIPCHK(hipEventRecord(d->ev1, s));
+    HIPCHK(hipEventSynchronize(d->ev1));
+    float t = 0.0f;
+    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
+    *ms = t / (float)iters;
+    return 0;
+}
+
+}  // namespace qh
+
+using namespace qh;
+
+extern "C" {
+
+int qdsp_hip_deemp_create(void** h, int device, int kind, int nchan, int max_block) {
+    if (!h) return QDSP_HIP_EINVAL;
+    *h = nullptr;
+    if ((kind != QDSP_HIP_DEEMP_MONO && kind != QDSP_HIP_DEEMP_STEREO) || nchan < 1 || nchan > kDemodMaxChan || max_block < 0)
+        return QDSP_HIP_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
+    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
+    HIPCHK(hipSetDevice(device));
+    Deemp* d = new (std::nothrow) Deemp();
+    if (!d) return QDSP_HIP_ENOMEM;
+    d->device = device;
+    d->kind = kind;
+    d->nchan = nchan;
+    d->max_block = max_block;
+    d->alpha.assign(nchan, 1.0f);   // sample_rate 1, tau 0 until set: y = x
+    const int nc = comps(d);
+    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
+    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
+    const size_t io_b = (size_t)max_block * nc * sizeof(float);
+    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, io_b);
+    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, io_b);
+    for (int i = 0; i < 2 && err == hipSuccess; i++) {
+        err = hipMalloc(&d->d_state[i], (size_t)nchan * nc * sizeof(double));
+        if (err == hipSuccess) err = hipMemset(d->d_state[i], 0, (size_t)nchan * nc * sizeof(double));
+    }
+    if (err == hipSuccess) err = hipMalloc(&d->d_alpha, (size_t)nchan * sizeof(float));
+    if (err == hipSuccess) err = hipMemcpy(d->d_alpha, d->alpha.data(), (size_t)nchan * sizeof(float), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMalloc(&d->d_part, (size_t)nchan * qk::kAmMaxParts * (1 + nc) * sizeof(double));
+    if (err != hipSuccess) {
+        deemp_free(d);
+        return -(int)err;
+    }
+    *h = d;
+    return 0;
+}
+int qdsp_hip_deemp_set(void* h, int chan, float sample_rate, float tau) {
+    Deemp* d = as_deemp(h);
+    if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
+    if (!std::isfinite(sample_rate) || sample_rate <= 0.0f || !std::isfinite(tau) || tau < 0.0f) return QDSP_HIP_EINVAL;
+    // BFMDeemp::init / setSampleRate / setTau (filter.h:102-103), in float
+    const float dt = 1.0f / sample_rate;
+    const float alpha = dt / (tau + dt);
+    if (!std::isfinite(alpha) || alpha <= 0.0f) return QDSP_HIP_EINVAL;
+    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
+    for (int c = c0; c < c1; c++) d->alpha[c] = alpha;
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
+    HIPCHK(hipMemcpy(d->d_alpha, d->alpha.data(), (size_t)d->nchan * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+int qdsp_hip_deemp_set_bypass(void* h, int on) {
+    Deemp* d = as_deemp(h);
+    if (!d) return QDSP_HIP_EINVAL;
+    d->bypass = on != 0;
+    return 0;
+}
+int qdsp_hip_deemp_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
+    Deemp* d = as_deemp(h);
+    return d ? deemp_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+}
+int qdsp_hip_deemp_process(void* h, const float* in, int count, float* out) {
+    return qdsp_hip_deemp_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
+}
+int qdsp_hip_deemp_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
+    Deemp* d = as_deemp(h);
+    return d ? deemp_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+}
+int qdsp_hip_deemp_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
+                                     void* hip_stream) {
+    Deemp* d = as_deemp(h);
+    return d ? deemp_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+}
+int qdsp_hip_deemp_get_state(void* h, int chan, float* l, float* r) {
+    Deemp* d = as_deemp(h);
+    if (!d || !chan_ok(d, chan) || !l || (comps(d) == 2 && !r)) return QDSP_HIP_EINVAL;
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipDeviceSynchronize());
+    double v[2] = {0.0, 0.0};
+    const int nc = comps(d);
+    HIPCHK(hipMemcpy(v, d->d_state[d->cur] + (size_t)chan * nc, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
+    *l = (float)v[0];
+    if (r) *r = (float)v[nc - 1];
+    return 0;
+}
+int qdsp_hip_deemp_set_state(void* h, int chan, float l, float r) {
+    Deemp* d = as_deemp(h);
+    if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipDeviceSynchronize());
+    const int nc = comps(d), c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
+    std::vector<double> v((size_t)n * nc);
+    for (int i = 0; i < n; i++) {
+        v[(size_t)i * nc] = (double)l;
+        if (nc == 2) v[(size_t)i * nc + 1] = (double)r;
+    }
+    HIPCHK(hipMemcpy(d->d_state[d->cur] + (size_t)c0 * nc, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+int qdsp_hip_deemp_get_alpha(void* h, int chan, float* alpha) {
+    Deemp* d = as_deemp(h);
+    if (!d || !chan_ok(d, chan) || !alpha) return QDSP_HIP_EINVAL;
+    *alpha = d->alpha[chan];
+    return 0;
+}
+int qdsp_hip_deemp_reset(void* h) {
+    Deemp* d = as_deemp(h);
+    if (!d) return QDSP_HIP_EINVAL;
+    HIPCHK(hipSetDevice(d->device));
+    HIPCHK(hipDeviceSynchronize());
+    for (int i = 0; i < 2; i++) HIPCHK(hipMemset(d->d_state[i], 0, (size_t)d->nchan * comps(d) * sizeof(double)));
+    return 0;
+}
+void qdsp_hip_deemp_destroy(void* h) { deemp_free(as_deemp(h)); }
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // misc_ops.hip -- the element-wise two-input blocks of src/dsp/math.h (Add / Substract / Multiply), the synthetic IQ source of the
 // bench, completion events and the timing / introspection helpers of the harness.  Split out of qdsp_hip.hip in round 3.
 #include "engine.hip.h"
-#include "demod.hip.h"
+#include "deemp.hip.h"
 
 namespace qh {
 
@@ -168,6 +168,10 @@ int qdsp_hip_set_done_event(void* h, void* ev) {
         d->done_ev = static_cast<hipEvent_t>(ev);
         return 0;
     }
+    if (Deemp* d = as_deemp(h)) {
+        d->done_ev = static_cast<hipEvent_t>(ev);
+        return 0;
+    }
     Engine* e = any_engine(h);
     if (!e) return QDSP_HIP_EINVAL;
     e->done_ev = static_cast<hipEvent_t>(ev);
@@ -178,6 +182,7 @@ int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* bloc
     const Launch* l = nullptr;
     if (Chan* c = as_chan(h)) l = &c->last;
     else if (Demod* d = as_demod(h)) l = &d->last;
+    else if (Deemp* d = as_deemp(h)) l = &d->last;
     else if (Engine* e = any_engine(h)) l = &e->last;
     if (!l) return QDSP_HIP_EINVAL;
     if (name && name_len > 0) { strncpy(name, l->name, name_len - 1); name[name_len - 1] = 0; }
@@ -189,6 +194,7 @@ int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* bloc
 
 int qdsp_hip_time_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
     if (Demod* d = as_demod(h)) return demod_time(d, d_in, count, d_out, stream, iters, ms);
+    if (Deemp* d = as_deemp(h)) return deemp_time(d, d_in, count, d_out, stream, iters, ms);
     Engine* e = any_engine(h);
     return e ? time_process(e, d_in, count, d_out, stream, iters, ms) : QDSP_HIP_EINVAL;
 }

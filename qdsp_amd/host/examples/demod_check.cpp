@@ -9,6 +9,9 @@
 //                   SSBDemod (ssb, p1 = bandWidth, p2 = mode 0 USB / 1 LSB / 2 DSB) -> sink, at sample rate outSR.
 //                   dev: the VFO hands its blocks to the demodulator in device memory (the links the blocks set up
 //                   themselves); host: the same graph with that link moved to the host buffers.
+//   demod_check deemp <dev|host> <in.cf32> <out> <block> <offset> <inSR> <outSR> <bw> <deviation> <tau>
+//                   source -> VFO -> FMDemod -> BFMDeemp (dsp/deemp.h) -> sink; host: both links into and out of the FMDemod
+//                   on the host buffers.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -19,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include <dsp/deemp.h>
 #include <dsp/demodulator.h>
 #include <dsp/sink.h>
 #include <dsp/source.h>
@@ -63,7 +67,7 @@ template <class T> struct Writer {
     }
 };
 
-// source -> VFO -> [BLOCK] -> sink; waits until every input block has come out the far end
+// source -> VFO -> [BLOCKS] -> sink; waits until every input block has come out the far end
 template <class T, class MAKE>
 static int runGraph(const char* inPath, const char* outPath, int block, float off, float inSR, float outSR, float bw, bool hostLink,
                     MAKE make) {
@@ -73,14 +77,14 @@ static int runGraph(const char* inPath, const char* outPath, int block, float of
     const long nblocks = (long)((feed.data.size() + block - 1) / block);
     HandlerSource<complex_t> src(Feed::pull, &feed);
     VFO vfo(&src.out, off, inSR, outSR, bw);
-    generic_unnamed_block* blk = nullptr;
-    stream<T>* last = make(vfo.out, blk);
+    std::vector<generic_unnamed_block*> blks;      // in graph order
+    stream<T>* last = make(vfo.out, blks);
     if (hostLink) { vfo.out->releaseConsumer(); }   // the VFO writes its host buffers, the demodulator uploads them
     Writer<T> w;
     w.file.open(outPath, std::ios::binary);
     HandlerSink<T> sink(last, Writer<T>::push, &w);
     sink.start();
-    if (blk) { blk->start(); }
+    for (auto it = blks.rbegin(); it != blks.rend(); ++it) { (*it)->start(); }
     vfo.start();
     src.start();
     const auto t0 = std::chrono::steady_clock::now();
@@ -91,9 +95,9 @@ static int runGraph(const char* inPath, const char* outPath, int block, float of
     }
     src.stop();
     vfo.stop();
-    if (blk) { blk->stop(); }
+    for (auto* b : blks) { b->stop(); }
     sink.stop();
-    delete blk;
+    for (auto it = blks.rbegin(); it != blks.rend(); ++it) { delete *it; }
     w.file.close();
     printf("graph ok: %zu in, %ld out, %ld blocks, %s link\n", feed.data.size(), w.samples.load(), nblocks, hostLink ? "host" : "device");
     return 0;
@@ -105,7 +109,7 @@ int main(int argc, char** argv) {
     if (mode == "vfo" && argc >= 9) {
         const float off = (float)atof(argv[5]), inSR = (float)atof(argv[6]), outSR = (float)atof(argv[7]), bw = (float)atof(argv[8]);
         return runGraph<complex_t>(argv[2], argv[3], atoi(argv[4]), off, inSR, outSR, bw, false,
-                                   [](stream<complex_t>* s, generic_unnamed_block*&) { return s; });
+                                   [](stream<complex_t>* s, std::vector<generic_unnamed_block*>&) { return s; });
     }
     if (argc < 10) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
     const std::string link = argv[2];
@@ -118,19 +122,30 @@ int main(int argc, char** argv) {
     const float p1 = argc > 10 ? (float)atof(argv[10]) : 0.0f;
     const int p2 = argc > 11 ? atoi(argv[11]) : 0;
     // the demodulator block and its output stream
-    auto with = [](auto* d, generic_unnamed_block*& blk) { blk = d; return &d->out; };
+    auto with = [](auto* d, std::vector<generic_unnamed_block*>& blks) { blks.push_back(d); return &d->out; };
     if (mode == "fm")
         return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
-                               [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new FloatFMDemod(s, outSR, p1), b); });
+                               [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new FloatFMDemod(s, outSR, p1), b); });
     if (mode == "fms")
         return runGraph<stereo_t>(in, out, block, off, inSR, outSR, bw, hostLink,
-                                  [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new FMDemod(s, outSR, p1), b); });
+                                  [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new FMDemod(s, outSR, p1), b); });
     if (mode == "am")
         return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
-                               [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new AMDemod(s), b); });
+                               [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new AMDemod(s), b); });
     if (mode == "ssb")
         return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
-                               [&](stream<complex_t>* s, generic_unnamed_block*& b) { return with(new SSBDemod(s, outSR, p1, p2), b); });
+                               [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new SSBDemod(s, outSR, p1, p2), b); });
+    if (mode == "deemp" && argc > 11) {
+        const float tau = (float)atof(argv[11]);
+        return runGraph<stereo_t>(in, out, block, off, inSR, outSR, bw, hostLink,
+                                  [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) {
+                                      FMDemod* fm = new FMDemod(s, outSR, p1);
+                                      b.push_back(fm);
+                                      BFMDeemp* de = new BFMDeemp(&fm->out, outSR, tau);
+                                      if (hostLink) { fm->out.releaseConsumer(); }
+                                      return with(de, b);
+                                  });
+    }
     fprintf(stderr, "unknown mode %s\n", mode.c_str());
     return 2;
 }

@@ -576,3 +576,114 @@ class SsbDemod(_Demod, _NcoMixin):
 
 
 __all__ += ["FmDemod", "AmDemod", "SsbDemod", "ssb_phase_delta"]
+
+
+class Deemp(_Op):
+    """BFMDeemp (src/dsp/filter.h:90-173): y[i] = alpha x[i] + (1 - alpha) y[i-1], alpha = dt / (tau + dt) in float, run as
+    an FP64 prefix scan (include/qdsp_hip.h).  stereo=True: stereo_t rows, shape (n, 2), l and r filtered independently;
+    stereo=False: float rows.  `nchan` channels per launch, each with its own alpha and state.  numpy input: the host entry
+    point (one channel); a 1-D / (n, 2) torch tensor: *_process_dev; (nchan, n) / (nchan, n, 2): `process_batch`."""
+
+    _prefix = "qdsp_hip_deemp"
+
+    def __init__(self, sample_rate, tau, stereo: bool = True, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self._stereo = bool(stereo)
+        self._nc = 2 if stereo else 1
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, 1 if stereo else 0, self.nchan, max_block), "qdsp_hip_deemp_create")
+        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
+        taus = np.broadcast_to(np.asarray(tau, dtype=np.float32), (self.nchan,))
+        for c in range(self.nchan):
+            self.set(float(rates[c]), float(taus[c]), c)
+
+    def _shape(self, *lead):
+        return (*lead, 2) if self._stereo else tuple(lead)
+
+    def set(self, sample_rate: float, tau: float, chan: int = -1):
+        capi.check(self._fn("set")(self._h, int(chan), sample_rate, tau), "qdsp_hip_deemp_set")
+
+    def bypass(self, on: bool):
+        capi.check(self._fn("set_bypass")(self._h, int(bool(on))))
+
+    def alpha(self, chan: int = 0):
+        v = C.c_float()
+        capi.check(self._fn("get_alpha")(self._h, int(chan), C.byref(v)))
+        return np.float32(v.value)
+
+    def get_state(self, chan: int = 0):
+        """The carried output, rounded to float: (l, r), or one value (mono)."""
+        l, r = C.c_float(), C.c_float()
+        capi.check(self._fn("get_state")(self._h, int(chan), C.byref(l), C.byref(r)))
+        return (np.float32(l.value), np.float32(r.value)) if self._stereo else np.float32(l.value)
+
+    def set_state(self, l: float, r: float = 0.0, chan: int = -1):
+        capi.check(self._fn("set_state")(self._h, int(chan), l, r))
+
+    def reset(self):
+        capi.check(self._fn("reset")(self._h))
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 1 + self._nc:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        assert a.ndim == self._nc and (not self._stereo or a.shape[1] == 2), a.shape
+        n = a.shape[0]
+        y = np.empty(self._shape(max(n, 1)), dtype=np.float32)
+        capi.check(self._fn("process")(self._h, a.ctypes.data, n, y.ctypes.data), "qdsp_hip_deemp_process")
+        return y[:n]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == self._nc, "one contiguous row"
+        assert self.nchan == 1 and (not self._stereo or x.shape[1] == 2)
+        n = x.shape[0]
+        if out is None:
+            out = torch.empty(self._shape(max(n, 1)), dtype=torch.float32, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= n and out.dim() == x.dim()
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), "qdsp_hip_deemp_process_dev")
+        return out[:n]
+
+    def process_batch(self, x, out=None, count: int = None):
+        """Channel c = row c of the float32 tensor `x`, (nchan, n) or (nchan, n, 2) (rows may be padded: x.stride(0) beyond
+        the row, e.g. FmDemod.process_batch's output or a slice of it); out=x filters in place."""
+        import torch
+
+        nc = self._nc
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 + nc and x.shape[0] == self.nchan and x.stride(1) == nc
+        assert not self._stereo or (x.shape[2] == 2 and x.stride(2) == 1)
+        assert x.stride(0) % nc == 0
+        n = x.shape[1] if count is None else int(count)
+        if out is None:
+            out = torch.empty(self._shape(self.nchan, max(n, 1)), dtype=torch.float32, device=x.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.dim() == x.dim() and out.shape[0] == self.nchan
+        assert out.shape[1] >= n and out.stride(1) == nc and out.stride(0) % nc == 0
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0) // nc, out.data_ptr(), out.stride(0) // nc, stream),
+                   "qdsp_hip_deemp_process_batch_dev")
+        return out[:, :n]
+
+    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
+        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
+        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
+
+    def set_done_event(self, ev: int):
+        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
+
+    def time_dev(self, x, out, iters: int) -> float:
+        """Mean ms per launch of `iters` back-to-back process_dev calls over the one row `x` (qdsp_hip_time_process_dev)."""
+        import torch
+
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ms = C.c_float()
+        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.shape[0] // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
+        capi.check(rc, "qdsp_hip_time_process_dev")
+        return float(ms.value)
+
+
+__all__ += ["Deemp"]

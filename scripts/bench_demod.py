@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Throughput of the demodulators (qdsp_amd/csrc/demod.hip) on device-resident synthetic IQ.
+"""Throughput of the demodulators (qdsp_amd/csrc/demod.hip) and of the de-emphasis scan (deemp.hip) on device-resident synthetic IQ.
 
-    python scripts/bench_demod.py                  # writes profiles/r05_demod_rates.txt
+    python scripts/bench_demod.py                  # writes profiles/deemp_rates.txt (r05_demod_rates.txt: the run before the de-emphasis legs)
     python scripts/bench_demod.py --quick --no-write   # a few launches of every kernel (for a rocprofv3 --kernel-trace run)
 
 Legs: FM, FM stereo, AM and SSB on 2^27-sample calls and on reference-sized 1e6-sample calls; xlate_cf32 on the same input
 (SSB is its NCO with half the store bytes); chan64 (BASELINE configs[4]: 64 channels, 256 taps, decimate 64) on a 2^27-sample
-input alone and followed by a batched 64-channel FM demodulator on its device output.  Timing: HIP events on the launch stream
+input alone and followed by a batched 64-channel FM demodulator on its device output, and by FM stereo + the batched de-emphasis;
+deemp_stereo / deemp_mono: the de-emphasis scan alone on the FM legs' outputs (16 B / 8 B per sample algorithmic; at these sizes the
+scan runs as two passes and reads its input twice, so it moves 24 B / 12 B).  Timing: HIP events on the launch stream
 around windows of >= 0.5 s after a warm-up, the legs alternated over `--repeats` rounds; min and spread (max / min - 1) of the
 per-call time.  Bytes are algorithmic, from shapes: 8 B read + 4 B written per sample (FM, AM, SSB), 8 + 8 (FM stereo, xlate).
 Fractions are of 8 TB/s (MI355X HBM peak).  Kernel times proper come from a separate rocprofv3 --kernel-trace --stats run."""
@@ -18,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 PEAK = 8.0e12
-OUT = os.path.join(ROOT, "profiles", "r05_demod_rates.txt")
+OUT = os.path.join(ROOT, "profiles", "deemp_rates.txt")
 
 
 def main():
@@ -53,6 +55,15 @@ def main():
     ch_out = torch.empty((64, nco + 8), dtype=torch.complex64, device="cuda")
     chan_fm = ops.FmDemod(250e3 / 64, 5e3, nchan=64, max_block=0)
     fm_ch_out = torch.empty((64, nco), dtype=torch.float32, device="cuda")
+    chan_fms = ops.FmDemod(250e3 / 64, 5e3, stereo=True, nchan=64, max_block=0)
+    chan_de = ops.Deemp(250e3 / 64, 50e-6, nchan=64, max_block=0)
+    fms_ch_out = torch.empty((64, nco, 2), dtype=torch.float32, device="cuda")
+    de_ch_out = torch.empty((64, nco, 2), dtype=torch.float32, device="cuda")
+    de_s, de_m = ops.Deemp(250e3, 50e-6, max_block=0), ops.Deemp(250e3, 50e-6, stereo=False, max_block=0)
+    fms.process(x, s_out)          # what the de-emphasis legs read: FM audio
+    fm.process(x, f_out)
+    ds_in, dm_in = s_out.clone(), f_out.clone()
+    ds_out, dm_out = torch.empty_like(s_out), torch.empty_like(f_out)
 
     def leg(op, n, out):
         xi = x[:n]
@@ -65,6 +76,13 @@ def main():
         y = chn.process(x, ch_out)
         chan_fm.process_batch(y, fm_ch_out)
 
+    def chan_fms_deemp_leg():
+        y = chn.process(x, ch_out)
+        chan_de.process_batch(chan_fms.process_batch(y, fms_ch_out), de_ch_out)
+
+    def deemp_leg(op, src, dst, n):
+        return lambda: op.process(src[:n], dst[:n])
+
     legs = {}
     for n, tag in ((big, "2^27"), (ref, "1e6")):
         legs[f"fm {tag}"] = (leg(fm, n, f_out), n, 12.0)
@@ -72,8 +90,11 @@ def main():
         legs[f"am {tag}"] = (leg(am, n, f_out), n, 12.0)
         legs[f"ssb {tag}"] = (leg(ssb, n, f_out), n, 12.0)
         legs[f"xlate {tag}"] = (leg(xl, n, c_out), n, 16.0)
+        legs[f"deemp_stereo {tag}"] = (deemp_leg(de_s, ds_in, ds_out, n), n, 16.0)
+        legs[f"deemp_mono {tag}"] = (deemp_leg(de_m, dm_in, dm_out, n), n, 8.0)
     legs["chan64 2^27"] = (chan_only, big, 16.0 * (1 + 1 / 64))           # (bench.py's chan64 bytes: input + 64 outputs of 1/64)
     legs["chan64+fm 2^27"] = (chan_fm_leg, big, None)
+    legs["chan64+fm_stereo+deemp 2^27"] = (chan_fms_deemp_leg, big, None)
 
     if args.quick:
         for f, _, _ in legs.values():
@@ -106,20 +127,25 @@ def main():
 
     lines = ["# scripts/bench_demod.py: per-call ms (min over %d alternated windows of >= %.1f s, HIP events), spread = max/min - 1" % (args.repeats, args.window),
              "# bytes: algorithmic (FM / AM / SSB 12 B, FM stereo / xlate 16 B per sample); frac = bytes / min time / 8 TB/s",
-             "%-16s %12s %10s %8s %10s %7s" % ("leg", "samples", "ms", "spread", "GB/s", "frac")]
+             "# deemp: 16 B (stereo) / 8 B (mono) per sample algorithmic; both sizes run the two-pass form, which reads its input twice",
+             "%-28s %12s %10s %8s %10s %7s" % ("leg", "samples", "ms", "spread", "GB/s", "frac")]
     res = {}
     for name, (f, n, b) in legs.items():
         t = min(times[name])
         spread = max(times[name]) / t - 1
         res[name] = t
         if b is None:
-            lines.append("%-16s %12d %10.4f %7.1f%% %10s %7s" % (name, n, t, 100 * spread, "-", "-"))
+            lines.append("%-28s %12d %10.4f %7.1f%% %10s %7s" % (name, n, t, 100 * spread, "-", "-"))
         else:
             gbs = n * b / (t * 1e-3) / 1e9
-            lines.append("%-16s %12d %10.4f %7.1f%% %10.1f %7.3f" % (name, n, t, 100 * spread, gbs, gbs * 1e9 / PEAK))
+            lines.append("%-28s %12d %10.4f %7.1f%% %10.1f %7.3f" % (name, n, t, 100 * spread, gbs, gbs * 1e9 / PEAK))
     fm_add = res["chan64+fm 2^27"] - res["chan64 2^27"]
     lines.append("# chan64 -> batched 64-channel FM: +%.4f ms over chan64 alone (%.1f %%); the FM kernel's own bytes: %d samples x 12 B"
                  % (fm_add, 100 * fm_add / res["chan64 2^27"], 64 * nco))
+    de_add = res["chan64+fm_stereo+deemp 2^27"] - res["chan64 2^27"]
+    lines.append("# chan64 -> batched FM stereo -> batched de-emphasis: +%.4f ms over chan64 alone (%.1f %%)" % (de_add, 100 * de_add / res["chan64 2^27"]))
+    for tag in ("2^27", "1e6"):
+        lines.append("# deemp_stereo against fm_stereo, same algorithmic bytes (%s): %.3f of its rate" % (tag, res[f"fm_stereo {tag}"] / res[f"deemp_stereo {tag}"]))
     for tag in ("2^27", "1e6"):
         s_gbs = 12.0 / res[f"ssb {tag}"]
         x_gbs = 16.0 / res[f"xlate {tag}"]
@@ -143,7 +169,7 @@ def kernel_stats(db):
     groups = {}
     for name, gx, gy, wx, vgpr, scratch, lds, dur in rows:
         short = name.replace("void ", "").split("(")[0]
-        if not any(k in short for k in ("demod", "am_", "xlate_kernel", "chan_uniform")):
+        if not any(k in short for k in ("demod", "am_", "xlate_kernel", "chan_uniform", "deemp")):
             continue
         groups.setdefault((short, gx, gy, wx, vgpr, scratch, lds), []).append(dur * 1e-3)   # (ns)
     lines = ["# rocprofv3 --kernel-trace --stats of scripts/bench_demod.py --quick (3 launches per leg); durations in us",
@@ -157,12 +183,18 @@ def kernel_stats(db):
             frac = "%.3f" % ((1 << 27) * (12.0 if "ssb" in short else 16.0) / (min(d) * 1e-6) / PEAK)
         lines.append("%-44s %10d %4d %5d %6d %7d %4d %10.1f %10.1f %6s" % (short, gx, gy, vgpr, scratch, lds, len(d), min(d),
                                                                           statistics.median(d), frac))
+    for nc, by in ((2, 16.0), (1, 8.0)):
+        de = [min(d) for (short, gx, gy, *_), d in groups.items()
+              if gy == 1 and short in (f"qk::deemp_partial_kernel<{nc}>", f"qk::deemp_scan_kernel<{nc}>") and gx >= 1023 * 256]
+        if len(de) == 2:
+            lines.append("# de-emphasis (%d floats per sample) at 2^27 samples, both passes: %.1f us, frac %.3f on %d B per sample"
+                         % (nc, sum(de), (1 << 27) * by / (sum(de) * 1e-6) / PEAK, int(by)))
     am = [min(d) for (short, gx, gy, *_), d in groups.items() if short.startswith("qk::am_") and gy == 1 and gx == 1024 * 256]
     if len(am) == 2:
         lines.append("# AM at 2^27 samples, both passes: %.1f us, frac %.3f" % (sum(am), (1 << 27) * 12.0 / (sum(am) * 1e-6) / PEAK))
     txt = "\n".join(lines) + "\n"
     print(txt)
-    out = os.path.join(ROOT, "profiles", "r05_demod_kernel_stats.txt")
+    out = os.path.join(ROOT, "profiles", "deemp_kernel_stats.txt")
     with open(out, "w") as fo:
         fo.write(txt)
 
