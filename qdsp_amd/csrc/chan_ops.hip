@@ -24,12 +24,16 @@ void chan_destroy(Chan* c) {
     c->magic = 0;
     delete c;
 }
-// The uniform plan the fast path needs: 64 channels, interp 1, decim 64, <= 256 taps, and the
+// The shapes the uniform fast path serves (whatever the increments are): 64 channels, interp 1, decim 64 / 32 / 16 / 8, <= 256 taps.
+bool chan_uniform_geometry(const Chan* c) {
+    if (c->nchan != 64 || c->interp != 1 || c->ntaps < 1 || c->ntaps > 256) return false;
+    return c->decim == 64 || c->decim == 32 || c->decim == 16 || c->decim == 8;
+}
+// The uniform plan the fast path needs: that geometry, and the
 // channels' fixed-point phase increments equal to channel 0's plus c * (+-2^58) to within
 // float rounding of the (cos, sin) pairs they came from.  Fills sign / deviations.
 bool chan_uniform_plan(const Chan* c, int* inv, long long* ddelta) {
-    if (c->nchan != 64 || c->interp != 1 || c->ntaps < 1 || c->ntaps > 256) return false;
-    if (c->decim != 64 && c->decim != 32 && c->decim != 16 && c->decim != 8) return false;
+    if (!chan_uniform_geometry(c)) return false;
     const unsigned long long d0 = c->vfo[0]->dphase;
     const long long tol = (long long)(18446744073709551616.0 * 4e-7);
     for (int sign = 1; sign >= -1; sign -= 2) {
@@ -45,20 +49,59 @@ bool chan_uniform_plan(const Chan* c, int* inv, long long* ddelta) {
     return false;
 }
 
+// A bank of that geometry may change path between two calls -- a retune across the tolerance and back, set_mode(DIRECT) for a
+// while -- and the paths keep different histories: the uniform kernel the last P RAW input samples, shared (c->d_hist), the
+// per-channel and batched kernels each channel's ROTATED history (vfo[i]->d_hist).  So that no path starts from a stale one,
+// EVERY path leaves the raw history current (chan_keep_raw_hist behind a per-channel call), and the per-channel histories are
+// rebuilt from it -- rotated with the phases those samples would have had, set_history_dev -- by the first per-channel call
+// that follows uniform ones (chan_refresh_vfo_hist).
+int chan_ensure_hist(Chan* c) {
+    if (c->d_hist[0]) return 0;
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(hipMalloc(&c->d_hist[i], (size_t)c->ntaps * sizeof(float2)));
+        HIPCHK(hipMemset(c->d_hist[i], 0, (size_t)c->ntaps * sizeof(float2)));
+    }
+    HIPCHK(hipDeviceSynchronize());         // (once per bank: the zeros are there before any stream reads them)
+    return 0;
+}
+int chan_keep_raw_hist(Chan* c, const void* d_in, int64_t count, hipStream_t s) {
+    if (!chan_uniform_geometry(c) || count <= 0) return 0;
+    { int rc = chan_ensure_hist(c); if (rc) return rc; }
+    const int P = c->ntaps;
+    const float2* in = static_cast<const float2*>(d_in);
+    if (count >= P) {
+        HIPCHK(hipMemcpyAsync(c->d_hist[c->cur], in + (count - P), (size_t)P * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    } else {
+        float2* nx = reinterpret_cast<float2*>(c->d_hist[c->cur ^ 1]);
+        const float2* old = reinterpret_cast<const float2*>(c->d_hist[c->cur]);
+        HIPCHK(hipMemcpyAsync(nx, old + count, (size_t)(P - count) * sizeof(float2), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(nx + (P - count), in, (size_t)count * sizeof(float2), hipMemcpyDeviceToDevice, s));
+        c->cur ^= 1;
+    }
+    return 0;
+}
+int chan_refresh_vfo_hist(Chan* c, hipStream_t s) {
+    if (!c->vfo_hist_stale) return 0;
+    c->vfo_hist_stale = false;
+    if (!c->d_hist[0]) return 0;
+    for (Engine* e : c->vfo) {
+        if (e->H != c->ntaps) continue;
+        int rc = set_history_dev(e, c->d_hist[c->cur], s);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 // Tables and the shared history of the uniform fast path (allocated on first use).
 int chan_uniform_prepare(Chan* c) {
-    const int P = c->ntaps;
     const long double two_pi = 6.283185307179586476925286766559005768L;
+    { int rc = chan_ensure_hist(c); if (rc) return rc; }
     if (!c->d_taps) {
         std::vector<float2> tw(64);
         for (int m = 0; m < 64; m++) tw[m] = make_float2((float)cosl(two_pi * m / 64), (float)(-sinl(two_pi * m / 64)));
         HIPCHK(hipMalloc(&c->d_taps, 256 * sizeof(float2)));
         HIPCHK(hipMalloc(&c->d_tw64, 64 * sizeof(float2)));
         HIPCHK(hipMemcpy(c->d_tw64, tw.data(), 64 * sizeof(float2), hipMemcpyHostToDevice));
-        for (int i = 0; i < 2; i++) {
-            HIPCHK(hipMalloc(&c->d_hist[i], (size_t)P * sizeof(float2)));
-            HIPCHK(hipMemset(c->d_hist[i], 0, (size_t)P * sizeof(float2)));
-        }
     }
     const unsigned long long d0 = c->vfo[0]->dphase;
     if (!c->gt_valid || c->gt_dphase != d0) {
@@ -101,6 +144,10 @@ int chan_launch_uniform(Chan* c, const void* d_in, int64_t count, int64_t nout, 
     a.waves = 4;
     int nwg = 256 * 48;  // 3 resident per CU, 16 rounds (round 3: 12 -> 48: -2 %, profiles/r03_chan_tuning.txt; 3 / 6 / 12 / 48 re-measured in round 4: 2.556 / 2.507 / 2.489 / 2.440 ms)
     if (nwg > (a.ntiles + a.waves - 1) / a.waves) nwg = (a.ntiles + a.waves - 1) / a.waves;
+    {   // QDSP_HIP_CHAN_MAX_WG (tests): fewer workgroups, so that a wave walks several tiles -- the persistent loop -- at test sizes
+        const int cap = qk::knob(qk::K_CHAN_MAX_WG, 0);
+        if (cap > 0 && nwg > cap) nwg = cap;
+    }
     if (nwg < 1) nwg = 1;
     a.nwg = nwg;
     a.kcentre = (c->ntaps - 1) / 2;
@@ -120,6 +167,7 @@ int chan_launch_uniform(Chan* c, const void* d_in, int64_t count, int64_t nout, 
     int rc = qk::launch_chan_uniform(a, nwg + 1, s);
     if (rc) return rc;
     c->cur ^= 1;
+    c->vfo_hist_stale = true;           // the channels' own histories did not see this call
     for (int i = 0; i < 64; i++) c->vfo[i]->phase += (unsigned long long)count * c->vfo[i]->dphase;
     c->last.name = "chan_uniform_kernel";
     c->last.grid = nwg + 1;
@@ -330,12 +378,16 @@ int64_t chan_process_dev(Chan* c, const void* d_in, int64_t count, void* d_out, 
             return rc ? rc : nout;
         }
     }
+    { int rc = chan_refresh_vfo_hist(c, static_cast<hipStream_t>(stream)); if (rc) return rc; }
     {
         const int mode = c->mode ? c->mode : qk::knob(qk::K_FIR_MODE, 0);
         if (mode == 0 && count > 0 && chan_batch_wins(c, count)) {
             const int rc = chan_launch_batch(c, d_in, count, nout, d_out, out_stride, static_cast<hipStream_t>(stream));
-            if (rc == 0) return nout;
             if (rc < 0) return rc;
+            if (rc == 0) {
+                const int rk = chan_keep_raw_hist(c, d_in, count, static_cast<hipStream_t>(stream));
+                return rk ? rk : nout;
+            }
         }
     }
     for (int i = 0; i < c->nchan; i++) {
@@ -344,6 +396,7 @@ int64_t chan_process_dev(Chan* c, const void* d_in, int64_t count, void* d_out, 
         if (r < 0) return r;
     }
     c->last = c->vfo[0]->last;
+    { int rc = chan_keep_raw_hist(c, d_in, count, static_cast<hipStream_t>(stream)); if (rc) return rc; }
     return nout;
 }
 
@@ -457,8 +510,10 @@ int64_t qdsp_hip_chan_cf32_process_links(void* h, const void* in, int in_link, i
         HIPCHK(hipMemcpyAsync(c->d_in, in, (size_t)count * sizeof(float2), hipMemcpyHostToDevice, st));
         src = c->d_in;
     }
+    { int rh = chan_refresh_vfo_hist(c, st); if (rh) return rh; }
     const int rc = chan_launch_batch(c, src, count, nout, nullptr, 0, st, dst.data());
     if (rc != 0) return rc < 0 ? rc : QDSP_HIP_EINVAL;
+    { int rk = chan_keep_raw_hist(c, src, count, st); if (rk) return rk; }
     bool must_wait = in_link != QDSP_HIP_LINK_PIPELINED || any_dev_sync;   // a host / plain device input is released on return
     if (any_host) {
         if (done_event) HIPCHK(hipEventRecord(static_cast<hipEvent_t>(done_event), st));
@@ -481,6 +536,8 @@ int qdsp_hip_chan_cf32_move_channel_state(void* h, int chan, void* vfo, int to_v
     apply_pending_inc(v);
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipDeviceSynchronize());          // (rare: a bank is built or taken down)
+    { int rc = chan_refresh_vfo_hist(c, nullptr); if (rc) return rc; }   // the channel's own history, if uniform calls left it behind
+    HIPCHK(hipDeviceSynchronize());
     Engine* src = to_vfo ? e : v;
     Engine* dst = to_vfo ? v : e;
     dst->phase = src->phase;
@@ -518,6 +575,8 @@ int qdsp_hip_chan_cf32_reset(void* h) {
     HIPCHK(hipSetDevice(c->device));
     for (int i = 0; i < 2; i++)
         if (c->d_hist[i]) HIPCHK(hipMemset(c->d_hist[i], 0, (size_t)c->ntaps * sizeof(float2)));
+    HIPCHK(hipDeviceSynchronize());
+    c->vfo_hist_stale = false;          // every history is zero
     return 0;
 }
 int qdsp_hip_chan_cf32_history_len(void* h) {
@@ -531,16 +590,22 @@ int qdsp_hip_chan_cf32_set_history_dev(void* h, const void* d_hist, void* s) {
     HIPCHK(hipSetDevice(c->device));
     int inv;
     long long dd[64];
-    if (chan_uniform_plan(c, &inv, dd)) {
-        // shared history of the fast path: raw input (channel 0's mixer lives in the taps)
-        int rc = chan_uniform_prepare(c);
+    const bool uniform = chan_uniform_plan(c, &inv, dd);
+    if (uniform) { int rc = chan_uniform_prepare(c); if (rc) return rc; }
+    if (chan_uniform_geometry(c)) {
+        // shared history of the fast path: raw input (channel 0's mixer lives in the taps); kept by every path of such a bank
+        int rc = chan_ensure_hist(c);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(c->d_hist[c->cur], d_hist, (size_t)c->ntaps * sizeof(float2), hipMemcpyDeviceToDevice,
                               static_cast<hipStream_t>(s)));
     }
     const int mode = c->mode ? c->mode : qk::knob(qk::K_FIR_MODE, 0);
-    if (mode == 1 || !chan_uniform_plan(c, &inv, dd))
+    if (mode == 1 || !uniform) {
         for (Engine* e : c->vfo) { int rc = set_history_dev(e, d_hist, s); if (rc) return rc; }
+        c->vfo_hist_stale = false;
+    } else {
+        c->vfo_hist_stale = true;       // rebuilt from the raw history by the first per-channel call
+    }
     return 0;
 }
 int qdsp_hip_chan_cf32_advance(void* h, int64_t n) {

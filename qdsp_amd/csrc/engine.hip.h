@@ -162,6 +162,7 @@ struct Chan {
     float2* d_tw64 = nullptr;
     float* d_hist[2] = {nullptr, nullptr};   // P raw input samples (shared by all channels)
     int cur = 0;
+    bool vfo_hist_stale = false;   // uniform calls ran since the channels' own (rotated) histories were last current: rebuilt from d_hist on a path switch
     // batched per-channel form (resamp_any_batch_kernel): the prototype's [L][P] phase table and the per-channel
     // constants, re-uploaded when a channel is retuned or its buffers change (batch_key: what the table was built from)
     float* d_phases = nullptr;

@@ -307,3 +307,226 @@ def poison_check(bad, first, last, t, span):
     missing = np.flatnonzero(hold & ~bad)
     stray = np.flatnonzero(bad & (dist > span))
     return missing, stray
+
+
+# ------------------------------------------------------------------------------------------------ uniform channelizer
+# The 64-channel polyphase + DFT channelizer (chan_uniform_kernel) restated from its documented operator (header of
+# qdsp_amd/csrc/chan.hip).  Phases are the library's 64-bit fixed-point turns (2^64 = one turn), kept as wrapping uint64 /
+# Python ints, so a phase is exact whatever the stream position; only the final conversion to an angle rounds (2^-53 turn).
+_MASK64 = (1 << 64) - 1
+CHAN_TOL_TURNS = 4e-7           # chan_uniform_plan: largest deviation of an increment from the grid d0 +- c / 64
+
+
+def fx_of_inc(re, im):
+    """Fixed-point turns per sample of a float (cos, sin) phase increment: the angle of the ROUNDED pair, as the library
+    (turns_of / fx_of_turns, long double) and the oracle's exact-phase rotator (atan2 of the pair) take it."""
+    ld = np.longdouble
+    two_pi = ld(8) * np.arctan(ld(1))
+    t = np.arctan2(ld(np.float32(im)), ld(np.float32(re))) / two_pi
+    t = t - np.floor(t)
+    hi = int(np.floor(np.ldexp(t, 32)))                      # (two exact 32-bit halves: no reliance on int(longdouble) being exact)
+    lo = int(np.floor(np.ldexp(np.ldexp(t, 32) - ld(hi), 32)))
+    return ((hi << 32) + lo) & _MASK64
+
+
+def inc_of_turns(t):
+    """The float32 (cos, sin) pair nearest to exp(j 2 pi t)."""
+    a = 2.0 * np.pi * (float(t) % 1.0)
+    return float(np.float32(np.cos(a))), float(np.float32(np.sin(a)))
+
+
+def chan_uniform_plan(dphase):
+    """chan_uniform_plan (chan_ops.hip): (inv, deltas) if the 64 fixed-point increments are channel 0's plus c * (+-2^58) to
+    within 4e-7 turn -- inv: channel c at +c/64 turn per sample; deltas: signed deviations, delta_0 = 0 -- else None."""
+    if len(dphase) != 64:
+        return None
+    tol = int(18446744073709551616.0 * CHAN_TOL_TURNS)
+    for sign in (1, -1):
+        dev = []
+        for c in range(64):
+            d = (int(dphase[c]) - (int(dphase[0]) + sign * c * (1 << 58))) & _MASK64
+            dev.append(d - (1 << 64) if d >= (1 << 63) else d)
+        if all(-tol <= d <= tol for d in dev):
+            return sign > 0, dev
+    return None
+
+
+def _u64(v):
+    """Python ints (any sign, any size) -> uint64 modulo 2^64; never through a numpy conversion of the list, which would go by float64."""
+    return np.array([int(a) & _MASK64 for a in (v if isinstance(v, (list, tuple)) else [v])], dtype=np.uint64)
+
+
+def fx_phasor(ph):
+    """exp(j 2 pi ph / 2^64) of a uint64 array, complex128."""
+    return np.exp(2j * np.pi * (np.asarray(ph, np.uint64).astype(np.float64) * 2.0 ** -64))
+
+
+def _fx_outer(a, b):
+    """a[:, None] * b[None, :] modulo 2^64."""
+    with np.errstate(over="ignore"):
+        return np.multiply.outer(np.asarray(a, np.uint64), np.asarray(b, np.uint64))
+
+
+def _windows(buf, P, M, nout):
+    """rows n' = buf[n' M : n' M + P] (buf long enough)."""
+    return np.lib.stride_tricks.sliding_window_view(buf, P)[::M][:nout]
+
+
+class ChanUniform64:
+    """A 64-channel bank with the library's state -- per channel a fixed-point phase and increment, and the last P RAW input
+    samples -- and two operators on it, both FP64, both for one call x (nout = len(x) // M outputs per channel, window n'
+    starting at call-relative position j0 = n' M - P, i.e. restarting with every call like PolyphaseResampler):
+
+      uniform(x): y_c[n'] = exp(j 2pi (j0 + kc) delta_c) sum_k h[k] x[j0 + k] exp(j 2pi (phi_c + (j0 + k)(dphi_c - delta_c)))
+                  -- the operator chan.hip documents: the deviation delta_c of channel c's increment from the grid applied at the
+                  window centre kc = (P - 1) // 2 instead of per tap;
+      exact(x):   y_c[n'] = sum_k h[k] x[j0 + k] exp(j 2pi (phi_c + (j0 + k) dphi_c)) -- rotate, then filter (Splitter -> VFO).
+
+    Broken-model switches (CPU controls only): kc_off moves the centre.  dphase overrides the increments (fixed point)."""
+
+    def __init__(self, taps, phase_incs, M, dphase=None, kc_off=0):
+        self.h = np.asarray(taps, np.float32).astype(np.float64)
+        self.P, self.M = len(self.h), int(M)
+        self.dphase = [int(d) & _MASK64 for d in dphase] if dphase is not None else [fx_of_inc(*pi) for pi in phase_incs]
+        self.phase = [0] * len(self.dphase)
+        self.hist = np.zeros(self.P, np.complex128)
+        self.kc = (self.P - 1) // 2 + kc_off
+
+    # -- state, as the C ABI moves it
+    def reset(self):
+        self.phase = [0] * len(self.dphase)
+        self.hist[:] = 0
+
+    def advance(self, n):
+        self.phase = [(p + n * d) & _MASK64 for p, d in zip(self.phase, self.dphase)]
+
+    def set_phase_inc(self, c, re, im):
+        self.dphase[c] = fx_of_inc(re, im)
+
+    def plan(self):
+        return chan_uniform_plan(self.dphase)
+
+    def _carry(self, buf, n):
+        self.hist = buf[n: n + self.P].copy()
+        self.advance(n)
+
+    def _sum(self, x, base, extra):
+        """sum_k h[k] buf[n' M + k] exp(j 2pi k base_c), times exp(j 2pi (phi_c + j0 dphi_c + extra_c)): (64, nout)."""
+        n = len(x)
+        nout = n // self.M
+        buf = np.concatenate([self.hist, np.asarray(x).astype(np.complex128)])
+        if nout:
+            W = self.h[:, None] * fx_phasor(_fx_outer(np.arange(self.P, dtype=np.uint64), _u64(base)))
+            S = _windows(buf, self.P, self.M, nout) @ W
+            j0 = (np.arange(nout, dtype=np.int64) * self.M - self.P).view(np.uint64)
+            with np.errstate(over="ignore"):
+                rot = _fx_outer(j0, _u64(self.dphase)) + _u64(self.phase)[None, :] + _u64(extra)[None, :]
+            y = (S * fx_phasor(rot)).T
+        else:
+            y = np.zeros((len(self.dphase), 0), np.complex128)
+        self._carry(buf, n)
+        return y
+
+    def uniform(self, x):
+        inv, delta = self.plan()
+        return self._sum(x, [d - dl for d, dl in zip(self.dphase, delta)], [self.kc * dl for dl in delta])
+
+    def exact(self, x):
+        return self._sum(x, self.dphase, [0] * len(self.dphase))
+
+
+def chan_uniform_ref64(taps, phase_incs, M, x, cuts, **kw):
+    """The documented operator of the uniform channelizer over a stream cut into calls at `cuts`: (64, n_out) complex128."""
+    r = ChanUniform64(taps, phase_incs, M, **kw)
+    return np.concatenate([r.uniform(x[a:b]) for a, b in zip(cuts, cuts[1:])], axis=1)
+
+
+def chan_uniform_windows(ntaps, M, cuts):
+    """[first, last] stream positions of every output's P-tap window."""
+    f = np.concatenate([a + np.arange((b - a) // M, dtype=np.int64) * M - ntaps for a, b in zip(cuts, cuts[1:])])
+    return f, f + ntaps - 1
+
+
+def chan_uniform_yard_call(st, xs, kc_off=0, mu_no_P=False, flip_inv=False):
+    """One call of the kernel's own algorithm on the FP32 road from the state `st` (a ChanUniform64, left unchanged): the folded
+    taps g[k] = h[k] exp(j 2pi k dphi_0) formed in FP64 and rounded to complex64 (chan_uniform_prepare), the 64 branch sums
+    U[p] = sum_q g[64 q + p] x[j0 + 64 q + p] in complex64 in q order, a 64-point complex64 radix-2 DFT over mu = (p - P) mod 64
+    (forward for the descending plan, conjugate twiddles for the ascending one) and ONE multiply by the FP64 phasor
+    exp(j 2pi (phi_c + j0 dphi_c + kc delta_c +- c P / 64)) rounded to complex64.
+    Broken models for the CPU controls: kc_off (window centre off by that many taps), mu_no_P (branches numbered mu = p while the
+    +- c P / 64 correction stays), flip_inv (the other template sign: conjugated twiddles and sc flipped)."""
+    P, M = st.P, st.M
+    Q = -(-P // 64)
+    xs = np.asarray(xs, np.complex64)
+    nout = len(xs) // M
+    if not nout:
+        return np.zeros((64, 0), np.complex64)
+    inv, delta = st.plan()
+    if flip_inv:
+        inv = not inv
+    d0 = st.dphase[0]
+    g = np.zeros(256, np.complex64)
+    g[:P] = (st.h * fx_phasor(_fx_outer(np.arange(P, dtype=np.uint64), _u64(d0))[:, 0])).astype(np.complex64)
+    buf = np.concatenate([st.hist.astype(np.complex64), xs, np.zeros(256, np.complex64)])       # (zeros behind the call)
+    Xw = _windows(buf, 256, M, nout)
+    U = np.zeros((nout, 64), np.complex64)
+    for q in range(Q):
+        U = (U + Xw[:, 64 * q: 64 * q + 64] * g[None, 64 * q: 64 * q + 64]).astype(np.complex64)
+    T = np.zeros_like(U)
+    p = np.arange(64)
+    T[:, p if mu_no_P else (p - P) & 63] = U
+    D = fft_radix2(T, inverse=True) * np.float32(64) if inv else fft_radix2(T)
+    sc = [(c if inv else -c) for c in range(64)]
+    inc = [(d0 + dl + (s << 58)) & _MASK64 for dl, s in zip(delta, sc)]                          # == dphase_c for the true sign
+    j0 = (np.arange(nout, dtype=np.int64) * M - P).view(np.uint64)
+    with np.errstate(over="ignore"):
+        rot = _fx_outer(j0, _u64(inc)) + _u64(st.phase)[None, :] + _u64([(st.kc + kc_off) * dl + ((s * P) << 58) for dl, s in zip(delta, sc)])[None, :]
+    return (D * fx_phasor(rot).astype(np.complex64)).astype(np.complex64).T
+
+
+def chan_uniform_yardstick32(taps, phase_incs, M, x, cuts, dphase=None, **broken):
+    """chan_uniform_yard_call over a stream cut into calls at `cuts`, state carried like chan_uniform_ref64: (64, n_out) complex64."""
+    st = ChanUniform64(taps, phase_incs, M, dphase=dphase)
+    out = []
+    for a, b in zip(cuts, cuts[1:]):
+        out.append(chan_uniform_yard_call(st, x[a:b], **broken))
+        st._carry(np.concatenate([st.hist, np.asarray(x[a:b]).astype(np.complex128)]), b - a)
+    return np.concatenate(out, axis=1)
+
+
+def rotate_direct32(taps, dphase, phase, hist_raw, x, M):
+    """Yardstick of one channel on a per-channel (rotate-then-filter) kernel: the FP64-phase NCO on [raw history | x] rounded to
+    complex64, then the k-ordered FP32 chain of direct_fma32."""
+    P = len(taps)
+    buf = np.concatenate([np.asarray(hist_raw, np.complex128), np.asarray(x).astype(np.complex128)])
+    j = (np.arange(len(buf), dtype=np.int64) - P).view(np.uint64)
+    with np.errstate(over="ignore"):
+        r = (buf * fx_phasor(j * np.uint64(int(dphase) & _MASK64) + np.uint64(int(phase) & _MASK64))).astype(np.complex64)
+    return direct_fma32(taps, r[P:], M, hist=r[:P], resamp=True)
+
+
+def chan_tones(n, dphase, loud_end, loud=17, weak=(16, 18, 49, 0, 63), weak_db=-100.0, off=0.0013, seed=0):
+    """Check A's input for a 64-channel bank (FP64, not rounded): a 0 dBFS tone in channel `loud`'s band on [0, loud_end) and
+    weak tones throughout in the bands of `weak`.  Channel c's band centre is the frequency its NCO brings to 0: -dphi_c."""
+    ph = np.random.default_rng(seed).uniform(0, 2 * np.pi, 1 + len(weak))
+    f = lambda c: -(int(dphase[c]) * 2.0 ** -64) + off                                               # noqa: E731
+    x = gate(tone(n, f(loud), 1.0, phase=ph[0]), 0, loud_end)
+    for i, c in enumerate(weak):
+        x = x + tone(n, f(c), 10.0 ** (weak_db / 20.0), phase=ph[1 + i])
+    return x
+
+
+def chan_taps(ntaps, fc=0.4 / 64):
+    """A Blackman-windowed sinc of any length >= 1 for the 64-channel bank (cutoff at 0.4 of the channel spacing), float32."""
+    if ntaps < 3:
+        return np.array([1.0, 0.5][:ntaps], np.float32)
+    n = np.arange(ntaps, dtype=np.float64)
+    h = 2 * fc * np.sinc(2 * fc * (n - (ntaps - 1) / 2.0))
+    h *= 0.42 - 0.5 * np.cos(2 * np.pi * n / (ntaps - 1)) + 0.08 * np.cos(4 * np.pi * n / (ntaps - 1))
+    return (h / h.sum()).astype(np.float32)
+
+
+def chan_grid_incs(sign, detune=0.0, shift=0.0):
+    """64 float (cos, sin) increments on the grid sign * (c - 31.5) / 64 + shift turns per sample; detune: channels 1..63 moved
+    off it by +-detune turns, alternating (channel 0 defines the grid, so its own deviation is 0 by construction)."""
+    return [inc_of_turns(sign * (c - 31.5) / 64 + shift + (0.0 if c == 0 else detune * (1 if c & 1 else -1))) for c in range(64)]

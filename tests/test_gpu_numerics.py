@@ -10,6 +10,8 @@
   E. headroom (a measurement): the first power-of-two amplitude of DC / a bin-centred tone where a family's output stops
      being finite or exactly equivariant.  With NUMERICS_REPORT=<file> the measured ratios and headroom go there as JSON.
 
+The uniform channelizer (chan_uniform_kernel) has its own operator, reference and section at the end: checks A-F in every kernel form.
+
 Every family is pinned the way tests/test_gpu_parity.py pins it, and every call's kernel is asserted."""
 import json
 import os
@@ -21,7 +23,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _numerics as NU  # noqa: E402
 import oracle as O  # noqa: E402
-from conftest import kname  # noqa: E402
+from conftest import kname, rel_rms  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +41,10 @@ SPAN = {
     "mfma_rm": lambda L, M, nt, N: -(-3 * M // L),
     "os_complex": lambda L, M, nt, N: 2 * N,    # fir_fft (4096), fir_fft1k (1024), pfb_dec8/4 (4096-point segments)
     "os_real": lambda L, M, nt, N: 3 * N,       # two adjacent real segments per complex transform
+    # chan_uniform_kernel: the folded taps lie in a table of four rows of 64, zero behind the prototype.  Both forms multiply Q_eff =
+    # ceil(nt / 64) rows -- QF = 4 (193..256 taps) all four without a test, QF = 0 the run-time a.Q = ceil(nt / 64) of them, the rows
+    # past it are skipped, not multiplied by zero -- so the zero taps nt .. 64 Q_eff - 1 of the last row meet the samples AFTER the window
+    "chan_uniform": lambda L, M, nt, N: 64 * -(-nt // 64) - nt,
 }
 
 # name, (interp, decim, ntaps), real data?, env, FFT mode?, expected kernel names, span class, transform length
@@ -402,8 +408,8 @@ def test_headroom_measurement(ops, monkeypatch, fam):
 # ------------------------------------------------------------------------------------------------ channelizer (batched VFOs)
 # Channelizer with arbitrary offsets: all channels in one launch of the MFMA decimator or of the general direct kernel, each
 # channel = rotate (FP64 phase) + PolyphaseResampler.  (The uniform polyphase + 64-point DFT form, chan_uniform_kernel, applies
-# each channel's NCO deviation at the centre of the tap window -- not the rotate-then-filter operator these references restate --
-# so it is held to check C only.)
+# each channel's NCO deviation at the centre of the tap window -- not the rotate-then-filter operator these references restate:
+# it has its own reference and its own section at the end of this file.)
 CHAN = [
     ("chan_mfma_batch", {"QDSP_HIP_MF_BATCH_MIN_WORK": "0"}, "decim_mfma_batch_kernel", "mfma_dec"),
     ("chan_any_batch", {"QDSP_HIP_NO_MF_BATCH": "1"}, "resamp_any_batch_kernel", "direct"),
@@ -548,3 +554,353 @@ def test_families_covered(ops, monkeypatch):
     seen |= {"fir_fft_kernel" for n in seen if n in ("fir_fft_dma_kernel", "fir_fft_dmapk_kernel")}
     want = set(FAMILIES) | {"fir_fft_kernel"}
     assert want <= seen, sorted(want - seen)
+
+
+# ------------------------------------------------------------------------------------------------ uniform channelizer
+# chan_uniform_kernel<INV, M, QF, ., ., ST4> against ITS operator (NU.ChanUniform64.uniform: each channel's deviation from the grid
+# applied at the centre of the tap window) and the FP32 yardstick of its own algorithm (NU.chan_uniform_yard_call), channel by
+# channel and region by region.  A form = (M, sign of the grid, taps): INV = sign > 0, QF = 4 for 193..256 taps else 0; every form
+# runs with 16-byte stores (aligned output, even row stride), with 8-byte stores (odd row stride) and with QDSP_HIP_CHAN_MAX_WG=1
+# (one workgroup: each wave walks a quarter of the call's tiles through the persistent loop and its LDS-DMA re-request).
+CU_FORMS = [
+    (64, -1, 256), (64, -1, 192), (64, -1, 129), (64, -1, 37),
+    (64, +1, 255), (64, +1, 193), (64, +1, 100), (64, +1, 64), (64, +1, 1),
+    (32, -1, 193), (32, -1, 100), (32, -1, 1),
+    (32, +1, 256), (32, +1, 129),
+    (16, -1, 255), (16, -1, 64), (16, -1, 37),
+    (16, +1, 193), (16, +1, 192),
+    (8, -1, 256), (8, -1, 37),
+    (8, +1, 255), (8, +1, 100),
+]
+CU_TAPS = (256, 255, 193, 192, 129, 100, 64, 37, 1)
+CU_DETUNED = [(64, -1, 255), (32, +1, 192), (16, -1, 129), (8, +1, 100)]
+CU_QF0 = [(64, -1, 192), (32, -1, 100), (16, -1, 64), (8, -1, 37)]
+CU_INV = [(64, +1, 255), (32, +1, 256), (16, +1, 193), (8, +1, 255)]
+CU_OUTS = [0, 325, 327, 967, 1168]      # calls in outputs per channel: 20 tiles + 5 outputs (ends inside a tile), 2 outputs (shorter than any
+                                        # tile's span of 15 M + 256 samples: guarded staging alone), 40 tiles, 12 tiles + 9 outputs: 73 tiles
+CU_WEAK = (16, 18, 49, 0, 63)
+
+
+def _cu_id(f):
+    return f"M{f[0]}_{'asc' if f[1] > 0 else 'desc'}_{f[2]}"
+
+
+def _cu_qf(ntaps):
+    return 4 if ntaps > 192 else 0
+
+
+def _cu_cuts(M):
+    return [o * M for o in CU_OUTS]
+
+
+def _cu_incs(ops, sign):
+    """The plan of the other tests (float theta, libm cosf / sinf) and its mirror image: channel c at sign * (c - 31.5) / 64."""
+    return [ops.phase_delta(1.0, sign * (c - 31.5) / 64) for c in range(64)]
+
+
+def _cu_run(ops, taps, M, incs, x, cuts, stride="even", volk=False, grids=None):
+    import torch
+
+    ch = ops.Channelizer(taps, 1, M, incs, max_block=0)
+    ch.set_volk_gain(volk)
+    ys = []
+    for a, b in zip(cuts, cuts[1:]):
+        no = (b - a) // M
+        out = torch.empty((64, max(2, (no + 1) & ~1) + (stride == "odd")), dtype=torch.complex64, device="cuda")
+        assert out.data_ptr() % 16 == 0 and out.shape[1] % 2 == (stride == "odd")      # 16-byte stores exactly when the stride is even
+        y = ch.process(torch.from_numpy(np.ascontiguousarray(x[a:b])).cuda(), out)
+        lk = ch.last_kernel()
+        assert lk["name"] == "chan_uniform_kernel", lk
+        if grids is not None:
+            grids.append(lk["grid"])
+        ys.append(y.cpu().numpy())
+    return np.concatenate(ys, axis=1)
+
+
+def _cu_three_runs(ops, monkeypatch, taps, M, incs, x, cuts, **kw):
+    """The call sequence with 16-byte stores, with one workgroup, and with 8-byte stores: (y, y_capped, y_odd_stride)."""
+    g0, g1 = [], []
+    monkeypatch.delenv("QDSP_HIP_CHAN_MAX_WG", raising=False)
+    y = _cu_run(ops, taps, M, incs, x, cuts, grids=g0, **kw)
+    yo = _cu_run(ops, taps, M, incs, x, cuts, stride="odd", **kw)
+    monkeypatch.setenv("QDSP_HIP_CHAN_MAX_WG", "1")
+    yc = _cu_run(ops, taps, M, incs, x, cuts, grids=g1, **kw)
+    monkeypatch.delenv("QDSP_HIP_CHAN_MAX_WG", raising=False)
+    tiles = [-(-((b - a) // M) // 16) for a, b in zip(cuts, cuts[1:])]
+    assert g0 == [max(1, -(-t // 4)) + 1 for t in tiles] and g1 == [2] * len(tiles), (g0, g1)      # (+ 1: the history workgroup)
+    return y, yc, yo
+
+
+def _cu_same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def _cu_region_check(y, yard, ref, regions, tag):
+    """All 64 rows inside K x the yardstick, region by region; returns the worst ratio per region."""
+    worst = {k: 0.0 for k in regions}
+    for c in range(64):
+        ok, rep = NU.region_check(y[c], yard[c], ref[c], regions)
+        assert ok, (tag, c, rep)
+        for k, v in rep.items():
+            if np.isfinite(v["ratio"]):
+                worst[k] = max(worst[k], v["ratio"])
+    return {k: round(v, 3) for k, v in worst.items()}
+
+
+def _cu_check_a(ops, monkeypatch, form, incs, tag):
+    M, sign, ntaps = form
+    taps = NU.chan_taps(ntaps)
+    cuts = _cu_cuts(M)
+    loud_end = cuts[-1] // 3
+    dphase = [NU.fx_of_inc(*p) for p in incs]
+    plan = NU.chan_uniform_plan(dphase)
+    assert plan is not None and plan[0] == (sign > 0)
+    x = NU.to32(NU.chan_tones(cuts[-1], dphase, loud_end, weak=CU_WEAK, seed=ntaps + M))
+    y, yc, yo = _cu_three_runs(ops, monkeypatch, taps, M, incs, x, cuts)
+    assert _cu_same_bits(yc, y), (tag, "which wave runs a tile changed a bit", np.argwhere(yc != y)[:4])
+    assert _cu_same_bits(yo, y), (tag, "the two store forms differ", np.argwhere(yo != y)[:4])
+    ref = NU.chan_uniform_ref64(taps, incs, M, x, cuts)
+    yard = NU.chan_uniform_yardstick32(taps, incs, M, x, cuts)
+    assert y.shape == ref.shape == (64, CU_OUTS[-1])
+    first, last = NU.chan_uniform_windows(ntaps, M, cuts)
+    regions = NU.loud_quiet_masks(first, last, loud_end, SPAN["chan_uniform"](1, M, ntaps, None), ref.shape[1])
+    assert regions["loud"].sum() > 300 and regions["quiet"].sum() > 600
+    # measured first, asserted after: the loud-region floor (RMS error) of the channels that carry no blocker
+    quiet_ch = [c for c in range(64) if c != 17]
+    floor = max(NU.region_err(y[c], ref[c], regions["loud"])[0] for c in quiet_ch)
+    yfloor = max(NU.region_err(yard[c], ref[c], regions["loud"])[0] for c in quiet_ch)
+    _REPORT.setdefault("chan_uniform_loud_floor", {})[tag] = {"kernel": float(f"{floor:.3e}"), "yardstick": float(f"{yfloor:.3e}"),
+                                                              "blocker_channel": float(f"{NU.region_err(y[17], ref[17], regions['loud'])[0]:.3e}"),
+                                                              "quiet_region_worst": float(f"{max(NU.region_err(y[c], ref[c], regions['quiet'])[1] for c in range(64)):.3e}")}
+    print(tag, _REPORT["chan_uniform_loud_floor"][tag])
+    _REPORT["ratios"][tag] = _cu_region_check(y, yard, ref, regions, tag)
+    print(tag, _REPORT["ratios"][tag])
+    # the quiet region's floor follows the weak tones (1e-5 x FP32 rounding), not the blocker that has left
+    assert max(NU.region_err(y[c], ref[c], regions["quiet"])[1] for c in range(64)) < 1e-10
+
+
+@pytest.mark.parametrize("form", CU_FORMS, ids=_cu_id)
+def test_chan_uniform_forms_blocker_and_weak_channels(ops, monkeypatch, form):
+    """Check A in every form: a 0 dBFS tone in channel 17's band for the first third, -100 dB tones throughout in 16, 18, 49 (17's
+    radix partner), 0 and 63, channel 40 empty; all 64 rows, loud and quiet region apart.  The capped and the odd-stride run: same bits."""
+    _pin(monkeypatch, {})
+    _cu_check_a(ops, monkeypatch, form, _cu_incs(ops, form[1]), "chan_uniform_" + _cu_id(form))
+
+
+@pytest.mark.parametrize("form", CU_DETUNED, ids=_cu_id)
+def test_chan_uniform_detuned_plan(ops, monkeypatch, form):
+    """Check A': increments 3e-7 turn off the grid, alternating in sign -- still a uniform plan (4e-7 admitted), the second-order
+    term of the per-output deviation rotation on (a.quad, chan_launch_uniform's rule restated), the window-centre term 30 x FP32."""
+    _pin(monkeypatch, {})
+    M = form[0]
+    incs = NU.chan_grid_incs(form[1], detune=3e-7)
+    _, delta = NU.chan_uniform_plan([NU.fx_of_inc(*p) for p in incs])
+    dmax = max(abs(d) for d in delta)
+    assert 2.5e-7 < dmax * 2.0 ** -64 < 3.5e-7
+    assert 15.0 * float(dmax) * M * 3.4061215800865545e-19 > 1e-4          # a.quad
+    _cu_check_a(ops, monkeypatch, form, incs, "chan_uniform_detuned_" + _cu_id(form))
+
+
+# ---- B
+def _cu_poison_positions(M):
+    cuts = _cu_cuts(M)
+    return {"first": cuts[2], "last": cuts[3] - 1, "history": cuts[1] + 1, "staged": cuts[2] + 20 * 16 * M + 3}
+
+
+@pytest.mark.parametrize("form", CU_QF0 + CU_INV, ids=_cu_id)
+def test_chan_uniform_nan_inf_locality(ops, monkeypatch, form):
+    """Check B.  A bad sample at the first / the last sample of the 40-tile call, in the 2-output call before it (it reaches the
+    long call through the history alone) and in the middle of the long call (at M = 8: inside the staged span that sixteen
+    overlapping windows share): in ALL 64 channels the outputs whose window holds it are bad, nothing beyond the span is, the
+    rest is inside the region bound of the clean stream, and one workgroup poisons the same set."""
+    _pin(monkeypatch, {})
+    M, sign, ntaps = form
+    taps, incs, cuts = NU.chan_taps(ntaps), _cu_incs(ops, sign), _cu_cuts(M)
+    span = SPAN["chan_uniform"](1, M, ntaps, None)
+    _REPORT.setdefault("chan_uniform_span", {})[_cu_id(form)] = {"QF": _cu_qf(ntaps), "Q_eff": -(-ntaps // 64), "span": span}
+    first, last = NU.chan_uniform_windows(ntaps, M, cuts)
+    xc = O.synth_iq(0, cuts[-1], seed=31)
+    for where, t in _cu_poison_positions(M).items():
+        x0 = xc.copy()
+        x0[t] = 0
+        ref0 = NU.chan_uniform_ref64(taps, incs, M, x0, cuts)
+        yard0 = NU.chan_uniform_yardstick32(taps, incs, M, x0, cuts)
+        far = np.maximum(0, np.maximum(first - t, t - last)) > span
+        hold = (first <= t) & (t <= last)
+        assert hold.sum() >= -(-ntaps // M) - 1 and far.sum() > 1000
+        for value in (np.nan, np.inf, -np.inf):
+            for comp in ("re", "im"):
+                x = xc.copy()
+                x[t] = complex(value, x[t].imag) if comp == "re" else complex(x[t].real, value)
+                monkeypatch.delenv("QDSP_HIP_CHAN_MAX_WG", raising=False)
+                y = _cu_run(ops, taps, M, incs, x, cuts)
+                bad = ~np.isfinite(y)
+                for c in range(64):
+                    missing, stray = NU.poison_check(bad[c], first, last, t, span)
+                    assert len(missing) == 0 and len(stray) == 0, (_cu_id(form), c, where, value, comp, missing[:4], stray[:4])
+                _cu_region_check(y, yard0, ref0, {"far": far}, (_cu_id(form), where, value, comp))
+                if comp == "re" and not np.isnan(value) or comp == "im" and np.isnan(value):
+                    continue
+                monkeypatch.setenv("QDSP_HIP_CHAN_MAX_WG", "1")
+                assert np.array_equal(~np.isfinite(_cu_run(ops, taps, M, incs, x, cuts)), bad), (_cu_id(form), where, value, comp)
+    monkeypatch.delenv("QDSP_HIP_CHAN_MAX_WG", raising=False)
+
+
+# ---- C / D
+@pytest.mark.parametrize("form", CU_QF0 + CU_INV, ids=_cu_id)
+def test_chan_uniform_scale_and_subnormals(ops, monkeypatch, form):
+    _pin(monkeypatch, {})
+    M, sign, ntaps = form
+    taps, incs, cuts = NU.chan_taps(ntaps), _cu_incs(ops, sign), _cu_cuts(M)
+    x = O.synth_iq(0, cuts[-1], seed=32)
+    y = _cu_run(ops, taps, M, incs, x, cuts)
+    for k in SCALES:
+        yk = _cu_run(ops, taps, M, incs, np.ldexp(x.view(np.float32), k).view(np.complex64), cuts)
+        assert _same_scaled(yk, y, k), (_cu_id(form), k)
+    xs = np.ldexp(x.view(np.float32), -140).view(np.complex64)
+    assert np.count_nonzero(np.abs(xs) < 2.0 ** -126) > len(xs) // 2
+    ys = _cu_run(ops, taps, M, incs, xs, cuts)
+    ref = NU.chan_uniform_ref64(taps, incs, M, xs, cuts)
+    err = np.abs(ys - ref).max()
+    print(_cu_id(form), "subnormal max err / bound", err / (2.0 ** -120 * np.abs(taps.astype(np.float64)).sum()), "zeros", float(np.mean(ys == 0)))
+    assert np.isfinite(ys).all() and err <= 2.0 ** -120 * np.abs(taps.astype(np.float64)).sum(), _cu_id(form)
+    _REPORT["subnormal_zero_fraction"]["chan_uniform_" + _cu_id(form)] = float(np.mean(ys == 0))
+    assert np.mean(ys == 0) < 0.05, (_cu_id(form), float(np.mean(ys == 0)))
+
+
+# ---- E
+@pytest.mark.parametrize("form", [(64, +1, 64), (16, -1, 64)], ids=_cu_id)
+def test_chan_uniform_volk_gain_against_oracle(ops, monkeypatch, form):
+    """Check E: VOLK's magnitude sawtooth on, against the oracle's exact-phase rotator with that gain + the F64 resampler at the
+    4e-6 of test_channelizer_64_channels -- an INV and a descending form, both QF = 0.
+    The oracle is rotate-then-filter, which the documented operator itself is not: its deviation term sits 2 pi max|delta_c|
+    sigma_k away (sigma_k: the taps' RMS distance from the window centre, weighted by h^2 -- white input), whatever computes it.
+    On the float-theta plan max|delta_c| = 6.2e-8 turn, so that is 2.8e-6 for these 64 taps (sigma_k 7.3) but 5.3e-6 for the 129
+    and 8.2e-6 for the 256 taps of NU.chan_taps (sigma_k 13.7, 21.1): the forms here are those whose operator leaves room under
+    4e-6 -- asserted below from the plan and the taps alone -- for the gain's own centre-of-window term (gm1 sigma_k < 3e-7) and FP32.
+    Measured: M32_asc_129 5.4e-6 in channel 63 (predicted 5.3e-6) when it was tried here; check A holds that form to its operator."""
+    _pin(monkeypatch, {})
+    M, sign, ntaps = form
+    taps, incs, cuts = NU.chan_taps(ntaps), _cu_incs(ops, sign), _cu_cuts(M)
+    _, delta = NU.chan_uniform_plan([NU.fx_of_inc(*p) for p in incs])
+    h2, k = taps.astype(np.float64) ** 2, np.arange(ntaps)
+    sigma_k = np.sqrt(np.sum(h2 * (k - (ntaps - 1) // 2) ** 2) / np.sum(h2))
+    assert 2 * np.pi * max(abs(d) for d in delta) * 2.0 ** -64 * sigma_k < 3e-6
+    x = O.synth_iq(0, cuts[-1], seed=33)
+    y, yc, yo = _cu_three_runs(ops, monkeypatch, taps, M, incs, x, cuts, volk=True)
+    assert _cu_same_bits(yc, y) and _cu_same_bits(yo, y)
+    for c in (0, 1, 17, 31, 32, 63):
+        xl = O.Xlator(1.0, sign * (c - 31.5) / 64, exact=True, volk_gain=True)
+        assert tuple(float(v) for v in xl.delta) == tuple(incs[c])
+        rs = O.Resampler(taps, 1, M, acc=O.ACC_F64)
+        want = np.concatenate([rs.process(xl.process(x[a:b])) for a, b in zip(cuts, cuts[1:])])
+        e = rel_rms(y[c], want)
+        print(_cu_id(form), c, "rel_rms", e)
+        assert e < 4e-6, (_cu_id(form), c, e)
+
+
+# ---- F
+def _cu_set_inc(ch, c, re, im):
+    from qdsp_amd import capi
+
+    capi.check(ch._L.qdsp_hip_chan_cf32_set_phase_inc(ch._h, int(c), float(re), float(im)))
+
+
+@pytest.mark.parametrize("form", [(16, -1, 100), (64, +1, 255)], ids=_cu_id)
+def test_chan_uniform_stream_state(ops, monkeypatch, form):
+    """Check F: the stateful ABI on a uniform bank, call by call against NU.ChanUniform64 carrying the same state: reset(),
+    advance(n), a retune of all 64 channels to a shifted grid (the folded taps are rebuilt), one channel retuned out of the 4e-7
+    tolerance and back and set_mode(DIRECT) for one call (the bank leaves the uniform kernel and comes back: the per-channel
+    kernels keep rotated per-channel histories, the uniform one the raw samples -- the first ceil(P / M) outputs after each switch
+    are the ones that see the other path's history, and they are checked as a region of their own), and three calls whose length
+    is no multiple of M: out_size promises floor(count / M) outputs, each call's windows starting at that call's first sample
+    minus P like PolyphaseResampler's, the history always the last P samples of the stream."""
+    import torch
+
+    _pin(monkeypatch, {})
+    M, sign, ntaps = form
+    taps, incs = NU.chan_taps(ntaps), _cu_incs(ops, sign)
+    head = -(-ntaps // M)
+    ch = ops.Channelizer(taps, 1, M, incs, max_block=0)
+    ch.set_volk_gain(False)
+    st = NU.ChanUniform64(taps, incs, M)
+    x = O.synth_iq(0, M * 2600, seed=34)
+    pos = [0]
+
+    def call(count, uniform, tag):
+        xs = x[pos[0]: pos[0] + count]
+        assert len(xs) == count
+        pos[0] += count
+        y = ch.process(torch.from_numpy(np.ascontiguousarray(xs)).cuda()).cpu().numpy()
+        name = ch.last_kernel()["name"]
+        assert (name == "chan_uniform_kernel") == uniform, (tag, name)
+        assert y.shape == (64, count // M) and ch.out_size(count) == count // M, (tag, y.shape)
+        if uniform:
+            assert st.plan() is not None
+            yard = NU.chan_uniform_yard_call(st, xs)
+            ref = st.uniform(xs)
+        else:
+            yard = np.array([NU.rotate_direct32(taps, st.dphase[c], st.phase[c], st.hist, xs, M) for c in range(64)])
+            ref = st.exact(xs)
+        h = np.arange(y.shape[1]) < head
+        regions = {"head": h, "rest": ~h} if (~h).any() else {"head": h}
+        rep = _cu_region_check(y, yard, ref, regions, (_cu_id(form), tag))
+        print(_cu_id(form), tag, name, rep)
+
+    def retune(c, re, im):
+        _cu_set_inc(ch, c, re, im)
+        st.set_phase_inc(c, re, im)
+
+    call(M * 325, True, "start")
+    ch.reset()
+    st.reset()
+    call(M * 200, True, "after reset")
+    ch.advance(12_345)
+    st.advance(12_345)
+    call(M * 100, True, "after advance")
+    shifted = NU.chan_grid_incs(sign, shift=0.0037)
+    for c in range(64):
+        retune(c, *shifted[c])
+    call(M * 150, True, "shifted grid")
+    off = NU.inc_of_turns(sign * (5 - 31.5) / 64 + 0.0037 + 1e-5)
+    retune(5, *off)
+    assert st.plan() is None
+    call(M * 120, False, "channel 5 off the grid")
+    call(M * 40, False, "still off the grid")
+    call(M * 3, False, "off the grid, a call shorter than the taps" if M * 3 < ntaps else "off the grid, a short call")
+    retune(5, *shifted[5])
+    call(M * 120, True, "back on the grid")
+    ch.set_mode(ch.DIRECT)
+    call(M * 60, False, "DIRECT for one call")
+    ch.set_mode(ch.AUTO)
+    call(M * 100, True, "AUTO again")
+    for count in (M * 50 + 5, M * 3 + 7, M * 60 + M - 1):
+        call(count, True, f"count {count} = {count % M} mod M")
+    call(M * 20, True, "whole calls again")
+
+
+# ---- coverage
+def test_chan_uniform_forms_covered(ops, monkeypatch):
+    """Every (INV, M, QF) instantiation is in CU_FORMS, each (M, sign) meets a QF = 0 and an odd-P plan, every tap count runs at
+    M = 64 and at an oversampled M -- and, one form per instantiation, a 40-tile call launches chan_uniform_kernel with 16-byte
+    stores, with 8-byte stores and with a single workgroup (the grid says so)."""
+    _pin(monkeypatch, {})
+    seen = {}
+    for M, sign, ntaps in CU_FORMS:
+        seen.setdefault((sign > 0, M, _cu_qf(ntaps)), (M, sign, ntaps))
+    assert set(seen) == {(inv, M, qf) for inv in (False, True) for M in (8, 16, 32, 64) for qf in (0, 4)}
+    for M in (8, 16, 32, 64):
+        for sign in (-1, 1):
+            mine = [f[2] for f in CU_FORMS if f[:2] == (M, sign)]
+            assert any(_cu_qf(t) == 0 for t in mine) and any(t % 2 for t in mine), (M, sign, mine)
+    for t in CU_TAPS:
+        assert (64, -1, t) in CU_FORMS or (64, 1, t) in CU_FORMS, t
+        assert any(f[2] == t and f[0] != 64 for f in CU_FORMS), t
+    assert {f[2] for f in CU_FORMS} == set(CU_TAPS)
+    for (inv, M, qf), form in sorted(seen.items()):
+        taps, incs = NU.chan_taps(form[2]), _cu_incs(ops, form[1])
+        plan = NU.chan_uniform_plan([NU.fx_of_inc(*p) for p in incs])
+        assert plan is not None and plan[0] == inv and (4 if -(-form[2] // 64) == 4 else 0) == qf
+        x = O.synth_iq(0, 640 * M, seed=35)
+        y, yc, yo = _cu_three_runs(ops, monkeypatch, taps, M, incs, x, [0, 640 * M])      # (asserts the kernel, the grids, the strides)
+        assert _cu_same_bits(yc, y) and _cu_same_bits(yo, y), form

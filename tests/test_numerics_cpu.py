@@ -182,3 +182,150 @@ def test_generators():
     assert np.all(NU.dc(8, 2.0) == 2.0) and NU.to32(NU.dc(8, 2.0)).dtype == np.complex64
     g = NU.gate(NU.tone(100, 0.1), 10, 20)
     assert np.count_nonzero(g) == 10 and NU.to32(NU.tone(8, 0.1, real=True)).dtype == np.float32
+
+
+# ------------------------------------------------------------------------------------------------ uniform channelizer
+CH_CUTS = {16: [0, 16 * 325, 16 * 327, 16 * 700], 64: [0, 64 * 325, 64 * 327, 64 * 700]}
+
+
+def _grid_dphase(sign):
+    d0 = NU.fx_of_inc(*NU.inc_of_turns(-sign * 31.5 / 64))
+    return [(d0 + sign * c * (1 << 58)) & ((1 << 64) - 1) for c in range(64)]
+
+
+def _rotate_then_filter(taps, dphase, M, x, cuts, chans):
+    out = {}
+    t = np.arange(len(x), dtype=np.uint64)
+    for c in chans:
+        with np.errstate(over="ignore"):
+            rot = x.astype(np.complex128) * NU.fx_phasor(t * np.uint64(dphase[c]))
+        r = NU.Resampler64(taps, 1, M)
+        out[c] = np.concatenate([r.process(rot[a:b]) for a, b in zip(cuts, cuts[1:])])
+    return out
+
+
+def test_fx_of_inc_is_the_angle_of_the_rounded_pair():
+    for t in (0.0, 0.1234, 0.5, 0.75, 31.5 / 64, 1e-7):
+        re, im = NU.inc_of_turns(t)
+        got = NU.fx_of_inc(re, im) * 2.0 ** -64
+        want = (np.arctan2(np.float64(np.float32(im)), np.float64(np.float32(re))) / (2 * np.pi)) % 1.0
+        assert abs((got - want + 0.5) % 1.0 - 0.5) < 1e-15, (t, got, want)
+    inv, delta = NU.chan_uniform_plan([NU.fx_of_inc(*p) for p in NU.chan_grid_incs(-1)])
+    assert not inv and delta[0] == 0 and 0 < max(abs(d) for d in delta) * 2.0 ** -64 < 1e-7
+    inv, delta = NU.chan_uniform_plan([NU.fx_of_inc(*p) for p in NU.chan_grid_incs(+1, detune=3e-7)])
+    assert inv and 2.5e-7 < max(abs(d) for d in delta) * 2.0 ** -64 < 3.5e-7
+    assert NU.chan_uniform_plan([NU.fx_of_inc(*p) for p in NU.chan_grid_incs(+1, detune=5e-7)]) is None
+
+
+@pytest.mark.parametrize("sign", [-1, 1])
+@pytest.mark.parametrize("M,ntaps", [(16, 100), (64, 255)])
+def test_chan_uniform_ref64_without_deviation_is_rotate_then_filter(sign, M, ntaps):
+    """(a) With every delta_c = 0 the documented operator IS rotate + PolyphaseResampler, to FP64 rounding -- all 64 channels,
+    a stream of three calls (one shorter than the taps)."""
+    taps = NU.chan_taps(ntaps)
+    dphase = _grid_dphase(sign)
+    assert NU.chan_uniform_plan(dphase) == (sign > 0, [0] * 64)
+    cuts = CH_CUTS[M]
+    x = O.synth_iq(0, cuts[-1], seed=21)
+    got = NU.chan_uniform_ref64(taps, None, M, x, cuts, dphase=dphase)
+    want = _rotate_then_filter(taps, dphase, M, x, cuts, range(64))
+    for c in range(64):
+        assert np.abs(got[c] - want[c]).max() <= 1e-12 * np.abs(want[c]).max(), c
+    # the per-channel operator of the same class (what a bank off the uniform plan computes) is the same thing
+    r = NU.ChanUniform64(taps, None, M, dphase=dphase)
+    ex = np.concatenate([r.exact(x[a:b]) for a, b in zip(cuts, cuts[1:])], axis=1)
+    assert np.abs(ex - got).max() <= 1e-12 * np.abs(got).max()
+
+
+@pytest.mark.parametrize("detune", [0.0, 3e-7])
+def test_chan_uniform_ref64_deviation_is_the_documented_approximation(detune):
+    """(b) With real deviations the restated operator differs from rotate-then-filter by the centre-of-window approximation and
+    no more: |e^{j 2pi (kc - k) delta} - 1| <= 2pi |delta| ntaps / 2 per tap."""
+    M, ntaps = 16, 255
+    taps = NU.chan_taps(ntaps)
+    incs = NU.chan_grid_incs(-1, detune=detune)
+    r = NU.ChanUniform64(taps, incs, M)
+    _, delta = r.plan()
+    dmax = max(abs(d) for d in delta) * 2.0 ** -64
+    assert (2.5e-7 < dmax < 3.5e-7) if detune else (0 < dmax < 1e-7)
+    cuts = CH_CUTS[M]
+    x = O.synth_iq(0, cuts[-1], seed=22)
+    got = NU.chan_uniform_ref64(taps, incs, M, x, cuts)
+    want = _rotate_then_filter(taps, r.dphase, M, x, cuts, range(64))
+    bound = 2 * np.pi * dmax * ntaps / 2
+    worst = 0.0
+    for c in range(64):
+        d = np.abs(got[c] - want[c])
+        assert d.max() <= bound * np.abs(taps.astype(np.float64)).sum() * np.abs(x).max(), c
+        rel = np.sqrt(np.mean(d * d) / np.mean(np.abs(want[c]) ** 2))
+        assert rel <= bound, (c, rel, bound)
+        worst = max(worst, rel)
+    assert worst > 1e-3 * bound          # ... and the deviation is really in there (FP64 rounding alone would sit at 1e-16)
+
+
+def _chan_check_a(taps, incs, M, y, ref, yard, cuts, loud_end, span):
+    first, last = NU.chan_uniform_windows(len(taps), M, cuts)
+    regions = NU.loud_quiet_masks(first, last, loud_end, span, ref.shape[1])
+    bad = []
+    for c in range(64):
+        ok, rep = NU.region_check(y[c], yard[c], ref[c], regions)
+        if not ok:
+            bad.append((c, {k: round(v["ratio"], 1) for k, v in rep.items()}))
+    return bad, regions
+
+
+def test_chan_uniform_three_channels_direct_sum():
+    """The matrix form of ChanUniform64 against the operator written out tap by tap, three channels."""
+    M, ntaps = 8, 37
+    taps = NU.chan_taps(ntaps)
+    incs = NU.chan_grid_incs(+1, detune=3e-7)
+    x = O.synth_iq(0, 8 * 40, seed=23)
+    r = NU.ChanUniform64(taps, incs, M)
+    r.advance(12345)
+    ph, dph = list(r.phase), list(r.dphase)
+    _, delta = r.plan()
+    y = r.uniform(x)
+    kc = (ntaps - 1) // 2
+    buf = np.concatenate([np.zeros(ntaps), x.astype(np.complex128)])
+    for c in (1, 17, 63):
+        for n in (0, 7, 39):
+            j0 = n * M - ntaps
+            acc = 0
+            for k in range(ntaps):
+                turns = ((ph[c] + (j0 + k) * (dph[c] - delta[c])) % (1 << 64)) / 2.0 ** 64
+                acc += float(taps[k]) * buf[n * M + k] * np.exp(2j * np.pi * turns)
+            acc *= np.exp(2j * np.pi * ((((j0 + kc) * delta[c]) % (1 << 64)) / 2.0 ** 64))
+            assert abs(acc - y[c, n]) <= 1e-12 * np.abs(y[c]).max(), (c, n)
+
+
+@pytest.mark.parametrize("M,ntaps,sign,detune", [(64, 100, -1, 0.0), (16, 255, 1, 3e-7)])
+def test_chan_uniform_yardstick_and_broken_models(M, ntaps, sign, detune):
+    """(c) Check A on the CPU: the FP32 yardstick sits FP32-close to the FP64 operator -- weak-tone-referred in the quiet region,
+    blocker-referred in the loud one, the empty channel 40 included -- and three wrong kernels fail the bound: the window centre
+    off by one tap (seen on the detuned plan: 2 pi 3e-7 rad is 30 x the FP32 floor), the DFT's branches numbered without the -P
+    (seen when P is no multiple of 64), and the other INV sign."""
+    taps = NU.chan_taps(ntaps)
+    incs = NU.chan_grid_incs(sign, detune=detune)
+    cuts = [0, M * 325, M * 327, M * 967, M * 1168]
+    n, loud_end = cuts[-1], cuts[-1] // 3
+    dphase = [NU.fx_of_inc(*p) for p in incs]
+    x = NU.to32(NU.chan_tones(n, dphase, loud_end))
+    ref = NU.chan_uniform_ref64(taps, incs, M, x, cuts)
+    yard = NU.chan_uniform_yardstick32(taps, incs, M, x, cuts)
+    span = 64 * -(-ntaps // 64) - ntaps
+    bad, regions = _chan_check_a(taps, incs, M, yard, ref, yard, cuts, loud_end, span)
+    assert not bad and regions["loud"].sum() > 300 and regions["quiet"].sum() > 600
+    for c in (17, 16, 40, 63):
+        loud, quiet = NU.region_err(yard[c], ref[c], regions["loud"]), NU.region_err(yard[c], ref[c], regions["quiet"])
+        assert quiet[1] < 1e-11 and loud[0] < 1e-6, (c, loud, quiet)
+    assert NU.region_err(yard[17], ref[17], regions["loud"])[0] > 1e-9          # the blocker's own FP32 floor
+    broken = {"inv": dict(flip_inv=True)}
+    if detune:
+        broken["kc"] = dict(kc_off=1)
+    if ntaps % 64:
+        broken["mu"] = dict(mu_no_P=True)
+    for name, kw in broken.items():
+        y = NU.chan_uniform_yardstick32(taps, incs, M, x, cuts, **kw)
+        bad, _ = _chan_check_a(taps, incs, M, y, ref, yard, cuts, loud_end, span)
+        assert bad, name
+        assert any(c == 17 for c, _ in bad), (name, bad[:4])
