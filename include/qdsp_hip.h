@@ -428,6 +428,57 @@ int qdsp_hip_deemp_get_alpha(void* h, int chan, float* alpha);
 int qdsp_hip_deemp_reset(void* h);
 void qdsp_hip_deemp_destroy(void* h);
 
+/* ---- level blocks : Squelch and AGC, src/dsp/processing.h:424-489 and :83-145 ------------- */
+/* Both take one reduction over a call (one run() of the reference) and one pass over it; nchan channel-major rows per launch,
+ * strides in samples, each channel with its own level / fall rate and its own state.  Rows of at most 4 tiles of 2048 samples
+ * (QDSP_HIP_LEVEL_ROW_TILES lowers that) take one launch that reads the row once (level_row_kernel); longer rows take two
+ * (level_partial_kernel, level_apply_kernel).  The state lives on the device; no call waits for it.  count == 0 is a no-op.
+ *   Squelch  complex rows in, complex rows out.  mean = the mean of |x| over the call, |x| = sqrtf(re*re + im*im) as VOLK's
+ *        generic magnitude, summed in FP64 in a fixed order and rounded once to float (the AM demodulator's rule: the order of
+ *        VOLK's float accumulator depends on the host's SIMD width).  The row is open when 10.0f * log10f(mean) >= level[chan],
+ *        evaluated on the device: an open row is a bit copy of the input, NaNs included; a closed row is +0.0f in every float.
+ *        A mean of 0 gives -inf: closed.  A NaN anywhere in the row makes the mean NaN, the comparison false and the row
+ *        closed, as in the reference.  level: -50.0f after create (processing.h:486).  get_open: the decision of the last
+ *        call, 0 after create / reset; it synchronises the device.
+ *   AGC  float rows in, float rows out.  level is 0 after create / reset.  Each call, on the device:
+ *          level = (float)pow(10.0, (double)(((10.0f * log10f(level)) - (cfr * (float)count)) / 10.0f))
+ *        with the inner expression in float and cfr = fall_rate / sample_rate in float (processing.h:93,123); then
+ *        level = max(level, max_i x[i]) under the reference's `x > level` (signed input as it is, no fabsf; a NaN never wins);
+ *        then out[i] = x[i] * (1.0f / level), one rounded reciprocal and one rounded product (volk_32f_s32f_multiply_32f).
+ *        Outputs and level are bit-identical to the reference loop wherever the call's maximum sets the level; where the
+ *        decayed level stands, it carries the device's log10f and pow (tests/test_level_cpu.py: agc_decay_bound).
+ *        The reference's corner cases are kept:  a level of 0 with no positive sample gives out = x * inf (+-inf, NaN for 0);
+ *        an Inf input pins the level at Inf (outputs 0, NaN at the Inf) until reset or set_level;  a NaN input yields a NaN
+ *        output at that sample only and leaves the level alone.
+ *        set(chan, fall_rate, sample_rate): default fall_rate 0, sample_rate 1; a sample_rate that is not finite and positive
+ *        or a fall_rate that is not finite is QDSP_HIP_EINVAL.  get_level synchronises the device.
+ * `chan` -1 = every channel (set_level, set).  process / process_ex (nchan 1): host pointers / link codes as for every
+ * *_process_ex, `count` <= max_block where a side is on the host (else QDSP_HIP_ESIZE).  process_dev: the nchan rows back to
+ * back (strides = count).  Device pointers: Squelch 8-byte, AGC 4-byte aligned; 16-byte aligned rows whose strides are whole
+ * 16-byte units take the vector loads and stores.  In place (d_out == d_in with out_stride == in_stride) is supported in both
+ * forms and gives the same bits; any other overlap of the spans of input and output is QDSP_HIP_EINVAL. */
+int qdsp_hip_squelch_create(void** h, int device, int nchan, int max_block);
+int qdsp_hip_squelch_set_level(void* h, int chan, float level_db);
+int qdsp_hip_squelch_get_open(void* h, int chan, int* open);
+int qdsp_hip_squelch_process(void* h, const float* in_iq, int count, float* out_iq);
+int qdsp_hip_squelch_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_squelch_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_squelch_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                       int64_t out_stride, void* hip_stream);
+int qdsp_hip_squelch_reset(void* h);
+void qdsp_hip_squelch_destroy(void* h);
+int qdsp_hip_agc_create(void** h, int device, int nchan, int max_block);
+int qdsp_hip_agc_set(void* h, int chan, float fall_rate, float sample_rate);
+int qdsp_hip_agc_get_level(void* h, int chan, float* level);
+int qdsp_hip_agc_set_level(void* h, int chan, float level);
+int qdsp_hip_agc_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_agc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_agc_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_agc_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                   int64_t out_stride, void* hip_stream);
+int qdsp_hip_agc_reset(void* h);
+void qdsp_hip_agc_destroy(void* h);
+
 /* ---- synthetic IQ source (measurement harness) ------------------------------ */
 /* Counter-based uniform [-1,1) per float component, generated on device so benchmarks are
  * HBM->HBM.  Bit-identical to oracle_synth_iq() for the same (first_sample, seed). */

@@ -197,6 +197,19 @@ def load():
     sig(p + "_get_alpha", i32, vp, i32, fp)
     sig(p + "_reset", i32, vp)
     sig(p + "_destroy", None, vp)
+    for p in ("qdsp_hip_squelch", "qdsp_hip_agc"):
+        sig(p + "_create", i32, pvp, i32, i32, i32)
+        sig(p + "_process", i32, vp, vp, i32, vp)
+        sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+        sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+        sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp)
+        sig(p + "_reset", i32, vp)
+        sig(p + "_destroy", None, vp)
+    sig("qdsp_hip_squelch_set_level", i32, vp, i32, C.c_float)
+    sig("qdsp_hip_squelch_get_open", i32, vp, i32, C.POINTER(i32))
+    sig("qdsp_hip_agc_set", i32, vp, i32, C.c_float, C.c_float)
+    sig("qdsp_hip_agc_get_level", i32, vp, i32, fp)
+    sig("qdsp_hip_agc_set_level", i32, vp, i32, C.c_float)
     sig("qdsp_hip_set_done_event", i32, vp, vp)
     sig("qdsp_hip_event_create", i32, i32, pvp)
     sig("qdsp_hip_event_destroy", i32, vp)

@@ -35,39 +35,6 @@ template <int NC> __device__ __forceinline__ Aff<NC> shfl_up(const Aff<NC>& v, i
     return r;
 }
 
-// the up to kDemodSpl samples at row[i0..) (NC floats each): 16-byte loads when the row is aligned and the lane's samples are all there
-template <int NC> __device__ __forceinline__ int load_lane(const float* row, long long i0, long long count, int vec, float (&x)[kDemodSpl * NC]) {
-    const long long rem = count - i0;
-    const int n = rem < 0 ? 0 : (rem < kDemodSpl ? (int)rem : kDemodSpl);
-    if (vec && n == kDemodSpl) {
-        const float4* p = reinterpret_cast<const float4*>(row + i0 * NC);
-#pragma unroll
-        for (int j = 0; j < kDemodSpl * NC / 4; j++) {
-            const float4 v = p[j];
-            x[4 * j] = v.x;
-            x[4 * j + 1] = v.y;
-            x[4 * j + 2] = v.z;
-            x[4 * j + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kDemodSpl * NC; j++) x[j] = (j < n * NC) ? row[i0 * NC + j] : 0.0f;
-    }
-    return n;
-}
-
-template <int NC> __device__ __forceinline__ void store_lane(float* row, long long i0, int n, int vec, const float (&y)[kDemodSpl * NC]) {
-    if (vec && n == kDemodSpl) {
-        float4* q = reinterpret_cast<float4*>(row + i0 * NC);
-#pragma unroll
-        for (int j = 0; j < kDemodSpl * NC / 4; j++) q[j] = make_float4(y[4 * j], y[4 * j + 1], y[4 * j + 2], y[4 * j + 3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < kDemodSpl * NC; j++)
-            if (j < n * NC) row[i0 * NC + j] = y[j];
-    }
-}
-
 // the lane's n samples as one map
 template <int NC> __device__ __forceinline__ Aff<NC> fold_lane(const float (&x)[kDemodSpl * NC], int n, double a, double b) {
     Aff<NC> p = aff_identity<NC>();

@@ -31,12 +31,6 @@ __device__ __forceinline__ float fm_out(float cp, float prev, float speed) {
     return w / speed;
 }
 
-// volk_32fc_magnitude_32f, generic kernel: sqrtf(re*re + im*im), each operation rounded
-__device__ __forceinline__ float am_mag(float2 v) {
-#pragma clang fp contract(off)
-    return sqrtf(v.x * v.x + v.y * v.y);
-}
-
 // the up to kDemodSpl samples at in[i0..): 16-byte loads when the row is aligned and the lane's samples are all there
 template <class F> __device__ __forceinline__ int for_samples(const float2* __restrict__ in, long long i0, long long count, int vec, F f) {
     const long long rem = count - i0;
@@ -57,19 +51,6 @@ template <class F> __device__ __forceinline__ int for_samples(const float2* __re
             if (j < n) f(j, in[i0 + j]);
     }
     return n;
-}
-
-// a workgroup's sum of one double per lane, always added in the same tree order
-__device__ __forceinline__ double block_sum(double s, double* red) {
-    const int t = threadIdx.x;
-    red[t] = s;
-    __syncthreads();
-#pragma unroll
-    for (int w = kDemodNT / 2; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    return red[0];
 }
 }  // namespace
 

@@ -36,6 +36,59 @@ struct AmArgs {
     int vec;
 };
 
+// ---- device helpers shared by demod.hip, deemp.hip and level.hip ----
+// volk_32fc_magnitude_32f, generic kernel: sqrtf(re*re + im*im), each operation rounded
+__device__ __forceinline__ float am_mag(float2 v) {
+#pragma clang fp contract(off)
+    return sqrtf(v.x * v.x + v.y * v.y);
+}
+
+// a workgroup's sum of one double per lane, always added in the same tree order
+__device__ __forceinline__ double block_sum(double s, double* red) {
+    const int t = threadIdx.x;
+    red[t] = s;
+    __syncthreads();
+#pragma unroll
+    for (int w = kDemodNT / 2; w > 0; w >>= 1) {
+        if (t < w) red[t] += red[t + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// the up to kDemodSpl samples at row[i0..) (NC floats each): 16-byte loads when the row is aligned and the lane's samples are all there
+template <int NC> __device__ __forceinline__ int load_lane(const float* row, long long i0, long long count, int vec, float (&x)[kDemodSpl * NC]) {
+    const long long rem = count - i0;
+    const int n = rem < 0 ? 0 : (rem < kDemodSpl ? (int)rem : kDemodSpl);
+    if (vec && n == kDemodSpl) {
+        const float4* p = reinterpret_cast<const float4*>(row + i0 * NC);
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC / 4; j++) {
+            const float4 v = p[j];
+            x[4 * j] = v.x;
+            x[4 * j + 1] = v.y;
+            x[4 * j + 2] = v.z;
+            x[4 * j + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC; j++) x[j] = (j < n * NC) ? row[i0 * NC + j] : 0.0f;
+    }
+    return n;
+}
+
+template <int NC> __device__ __forceinline__ void store_lane(float* row, long long i0, int n, int vec, const float (&y)[kDemodSpl * NC]) {
+    if (vec && n == kDemodSpl) {
+        float4* q = reinterpret_cast<float4*>(row + i0 * NC);
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC / 4; j++) q[j] = make_float4(y[4 * j], y[4 * j + 1], y[4 * j + 2], y[4 * j + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kDemodSpl * NC; j++)
+            if (j < n * NC) row[i0 * NC + j] = y[j];
+    }
+}
+
 }  // namespace qk
 
 namespace qh {

@@ -1,6 +1,5 @@
-// dsp/processing.h -- dsp::FrequencyXlator<T>, HIP-backed (the reference's other blocks in
-// this header -- AGC, squelch, packer ... -- are serial recurrences outside the hot path and
-// are not provided).
+// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch and dsp::AGC, HIP-backed (the reference's
+// other blocks in this header -- FeedForwardAGC, ComplexAGC, packer ... -- are not provided).
 //
 // Drop-in for src/dsp/processing.h:10-81.  init()/setSampleRate()/setFrequency() compute
 // phaseDelta exactly as the reference does -- theta = (freq/sampleRate) * 2.0f * FL_M_PI in
@@ -104,6 +103,177 @@ private:
     float _sampleRate = 1.0f, _freq = 0.0f;
     float deltaRe = 1.0f, deltaIm = 0.0f;
     stream<complex_t>* _in = nullptr;
+    void* handle = nullptr;
+    detail::done_events done;
+};
+
+
+// Squelch (src/dsp/processing.h:424-489): same constructors, init(), setInput(), setLevel(), getLevel() and `out`.  run() is one
+// call into libqdsp_hip (qdsp_hip_squelch_process_ex) with the device links of the other blocks, so VFO -> Squelch -> demodulator
+// hands its blocks over in device memory.  The mean of |x| is summed in FP64 on the device (include/qdsp_hip.h).
+class Squelch : public generic_block<Squelch> {
+    using base = generic_block<Squelch>;
+
+public:
+    Squelch() {}
+
+    Squelch(stream<complex_t>* in, float level) { init(in, level); }
+
+    ~Squelch() {
+        const bool live = base::running;
+        base::stop();
+        if (live && _in) { _in->releaseConsumer(); }
+        if (handle) { qdsp_hip_squelch_destroy(handle); }
+    }
+
+    void init(stream<complex_t>* in, float level) {
+        _in = in;
+        _level = level;
+        int rc = qdsp_hip_squelch_create(&handle, detail::hipDeviceForBlocks(), 1, STREAM_BUFFER_SIZE);
+        if (rc == 0) { rc = qdsp_hip_squelch_set_level(handle, 0, _level); }
+        if (rc != 0) { handle = nullptr; detail::hipBlockFail("Squelch::init", rc); }
+        base::registerInput(_in);
+        base::registerOutput(&out);
+        _in->claimConsumer(handle != nullptr, true);
+    }
+
+    void setInput(stream<complex_t>* in) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        base::unregisterInput(_in);
+        _in->releaseConsumer();
+        _in = in;
+        _in->claimConsumer(handle != nullptr, true);
+        base::registerInput(_in);
+        base::tempStart();
+    }
+
+    void setLevel(float level) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        _level = level;
+        if (handle) {
+            const int rc = qdsp_hip_squelch_set_level(handle, 0, _level);
+            if (rc != 0) { detail::hipBlockFail("Squelch::setLevel", rc); }
+        }
+        base::tempStart();
+    }
+
+    float getLevel() { return _level; }
+
+    int run() override {
+        const int count = _in->read();
+        if (count < 0) { return -1; }
+        if (!handle) { return -1; }
+        const bool inDev = _in->readOnDevice;
+        const bool outDev = out.consumerTakesDevice && out.ensureDevice(detail::hipDeviceForBlocks());
+        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
+        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
+        void* evt = nullptr;
+        const int outLink = outDev ? out.linkOut(true) : done.arm(handle, evt);
+        const int rc = qdsp_hip_squelch_process_ex(handle, src, _in->linkIn(), count, dst, outLink);
+        _in->flush();
+        if (rc != 0) { return detail::hipBlockFail("Squelch::run", rc); }
+        out.markWritten(outLink, evt);
+        if (!out.swap(count)) { return -1; }
+        return count;
+    }
+
+    stream<complex_t> out;
+
+private:
+    float _level = -50.0f;
+    stream<complex_t>* _in = nullptr;
+    void* handle = nullptr;
+    detail::done_events done;
+};
+
+// AGC (src/dsp/processing.h:83-145): same constructors, init(), setInput(), setSampleRate(), setFallRate() and `out`.  The level
+// lives on the device; _CorrectedFallRate = fallRate / sampleRate is computed by the library in float, as init() computes it.
+class AGC : public generic_block<AGC> {
+    using base = generic_block<AGC>;
+
+public:
+    AGC() {}
+
+    AGC(stream<float>* in, float fallRate, float sampleRate) { init(in, fallRate, sampleRate); }
+
+    ~AGC() {
+        const bool live = base::running;
+        base::stop();
+        if (live && _in) { _in->releaseConsumer(); }
+        if (handle) { qdsp_hip_agc_destroy(handle); }
+    }
+
+    void init(stream<float>* in, float fallRate, float sampleRate) {
+        _in = in;
+        _sampleRate = sampleRate;
+        _fallRate = fallRate;
+        int rc = qdsp_hip_agc_create(&handle, detail::hipDeviceForBlocks(), 1, STREAM_BUFFER_SIZE);
+        if (rc == 0) { rc = qdsp_hip_agc_set(handle, 0, _fallRate, _sampleRate); }
+        if (rc != 0) { handle = nullptr; detail::hipBlockFail("AGC::init", rc); }
+        base::registerInput(_in);
+        base::registerOutput(&out);
+        _in->claimConsumer(handle != nullptr, true);
+    }
+
+    void setInput(stream<float>* in) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        base::unregisterInput(_in);
+        _in->releaseConsumer();
+        _in = in;
+        _in->claimConsumer(handle != nullptr, true);
+        base::registerInput(_in);
+        base::tempStart();
+    }
+
+    void setSampleRate(float sampleRate) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        _sampleRate = sampleRate;
+        push();
+        base::tempStart();
+    }
+
+    void setFallRate(float fallRate) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        _fallRate = fallRate;
+        push();
+        base::tempStart();
+    }
+
+    int run() override {
+        const int count = _in->read();
+        if (count < 0) { return -1; }
+        if (!handle) { return -1; }
+        const bool inDev = _in->readOnDevice;
+        const bool outDev = out.consumerTakesDevice && out.ensureDevice(detail::hipDeviceForBlocks());
+        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
+        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
+        void* evt = nullptr;
+        const int outLink = outDev ? out.linkOut(true) : done.arm(handle, evt);
+        const int rc = qdsp_hip_agc_process_ex(handle, src, _in->linkIn(), count, dst, outLink);
+        _in->flush();
+        if (rc != 0) { return detail::hipBlockFail("AGC::run", rc); }
+        out.markWritten(outLink, evt);
+        if (!out.swap(count)) { return -1; }
+        return count;
+    }
+
+    stream<float> out;
+
+private:
+    void push() {
+        if (!handle) { return; }
+        const int rc = qdsp_hip_agc_set(handle, 0, _fallRate, _sampleRate);
+        if (rc != 0) { detail::hipBlockFail("AGC::setFallRate", rc); }
+    }
+
+    float _fallRate = 0.0f;
+    float _sampleRate = 1.0f;
+    stream<float>* _in = nullptr;
     void* handle = nullptr;
     detail::done_events done;
 };

@@ -12,6 +12,11 @@
 //   demod_check deemp <dev|host> <in.cf32> <out> <block> <offset> <inSR> <outSR> <bw> <deviation> <tau>
 //                   source -> VFO -> FMDemod -> BFMDeemp (dsp/deemp.h) -> sink; host: both links into and out of the FMDemod
 //                   on the host buffers.
+//   demod_check squelch <dev|host> <in.cf32> <out.cf32> <block> <offset> <inSR> <outSR> <bw> <level_db>
+//                   source -> VFO -> Squelch (dsp/processing.h) -> sink
+//   demod_check agc <dev|host> <in.cf32> <out> <block> <offset> <inSR> <outSR> <bw> <fall_rate>
+//                   source -> VFO -> AMDemod -> AGC (dsp/processing.h) -> sink; host: both links into and out of the AMDemod on
+//                   the host buffers.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -24,6 +29,7 @@
 
 #include <dsp/deemp.h>
 #include <dsp/demodulator.h>
+#include <dsp/processing.h>
 #include <dsp/sink.h>
 #include <dsp/source.h>
 #include <dsp/vfo.h>
@@ -146,6 +152,18 @@ int main(int argc, char** argv) {
                                       return with(de, b);
                                   });
     }
+    if (mode == "squelch" && argc > 10)
+        return runGraph<complex_t>(in, out, block, off, inSR, outSR, bw, hostLink,
+                                   [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new Squelch(s, p1), b); });
+    if (mode == "agc" && argc > 10)
+        return runGraph<float>(in, out, block, off, inSR, outSR, bw, hostLink,
+                               [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) {
+                                   AMDemod* am = new AMDemod(s);
+                                   b.push_back(am);
+                                   AGC* agc = new AGC(&am->out, p1, outSR);
+                                   if (hostLink) { am->out.releaseConsumer(); }
+                                   return with(agc, b);
+                               });
     fprintf(stderr, "unknown mode %s\n", mode.c_str());
     return 2;
 }

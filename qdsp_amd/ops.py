@@ -687,3 +687,130 @@ class Deemp(_Op):
 
 
 __all__ += ["Deemp"]
+
+
+class _Level(_Op):
+    """One reduction over a call, then one pass over it, per channel (include/qdsp_hip.h: level blocks).  numpy input: the host
+    entry point (one channel); a 1-D torch tensor: *_process_dev; a 2-D one: one row per channel (`process_batch`)."""
+
+    _np, _tt = np.float32, "float32"
+    nchan = 1
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=self._np)
+        assert a.ndim == 1, a.shape
+        y = np.empty(max(a.size, 1), dtype=self._np)
+        capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:a.size]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
+        n = x.numel()
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=dt, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= n
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
+        return out[:n]
+
+    def process_batch(self, x, out=None, count: int = None):
+        """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count, e.g. the Channelizer's output or
+        AmDemod.process_batch's, or a slice of it); out=x works in place."""
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        if out is None:
+            out = torch.empty((self.nchan, max(n, 1)), dtype=dt, device=x.device)
+        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == 1
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), stream),
+                   self._prefix + "_process_batch_dev")
+        return out[:, :n]
+
+    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
+        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
+        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
+
+    def set_done_event(self, ev: int):
+        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
+
+    def reset(self):
+        capi.check(self._fn("reset")(self._h))
+
+    def time_dev(self, x, out, iters: int) -> float:
+        """Mean ms per launch of `iters` back-to-back process_dev calls over the nchan rows of `x`, back to back
+        (qdsp_hip_time_process_dev)."""
+        import torch
+
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ms = C.c_float()
+        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.numel() // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
+        capi.check(rc, "qdsp_hip_time_process_dev")
+        return float(ms.value)
+
+
+class Squelch(_Level):
+    """dsp::Squelch (src/dsp/processing.h:424-489): a call whose mean |x| is at least `level` dB is copied, any other is
+    zeroed; `nchan` channels per launch, each with its own level (a scalar or one value per channel)."""
+
+    _prefix = "qdsp_hip_squelch"
+    _np, _tt = np.complex64, "complex64"
+
+    def __init__(self, level=-50.0, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_squelch_create")
+        levels = np.broadcast_to(np.asarray(level, dtype=np.float32), (self.nchan,))
+        for c in range(self.nchan):
+            self.set_level(float(levels[c]), c)
+
+    def set_level(self, level: float, chan: int = -1):
+        capi.check(self._fn("set_level")(self._h, int(chan), level), "qdsp_hip_squelch_set_level")
+
+    def is_open(self, chan: int = 0) -> bool:
+        """The decision of the last call (synchronises the device)."""
+        v = C.c_int()
+        capi.check(self._fn("get_open")(self._h, int(chan), C.byref(v)))
+        return bool(v.value)
+
+
+class Agc(_Level):
+    """dsp::AGC (src/dsp/processing.h:83-145): the call scaled by 1 / level; level decays by fall_rate / sample_rate dB per
+    sample and follows the call's maximum.  `nchan` channels per launch, each with its own rates and level."""
+
+    _prefix = "qdsp_hip_agc"
+
+    def __init__(self, fall_rate, sample_rate, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_agc_create")
+        falls = np.broadcast_to(np.asarray(fall_rate, dtype=np.float32), (self.nchan,))
+        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
+        for c in range(self.nchan):
+            self.set(float(falls[c]), float(rates[c]), c)
+
+    def set(self, fall_rate: float, sample_rate: float, chan: int = -1):
+        capi.check(self._fn("set")(self._h, int(chan), fall_rate, sample_rate), "qdsp_hip_agc_set")
+
+    def level(self, chan: int = 0):
+        """The carried level (synchronises the device)."""
+        v = C.c_float()
+        capi.check(self._fn("get_level")(self._h, int(chan), C.byref(v)))
+        return np.float32(v.value)
+
+    def set_level(self, level: float, chan: int = -1):
+        capi.check(self._fn("set_level")(self._h, int(chan), level))
+
+
+__all__ += ["Squelch", "Agc"]
