@@ -2,6 +2,7 @@
 the C++ block mirror carries the reference's names, build() makes the graph harness -- and the numpy float32 restatement of
 the FM and AM arithmetic that the GPU tests compare against is pinned, bit for bit, to the C++ host code it restates
 (complex_t::fastPhase of qdsp_amd/host/dsp/types.h, the FM loop of demodulator.h:86-95, VOLK's generic magnitude)."""
+import math
 import os
 import re
 import subprocess
@@ -63,6 +64,79 @@ def am_ref(x):
     """AMDemod::run with the mean taken in FP64 and rounded once: (outputs, avg)."""
     m = am_mag(x)
     avg = np.float32(np.sum(m.astype(np.float64)) / len(m)) if len(m) else np.float32(0)
+    return (m - avg).astype(np.float32), avg
+
+
+def fm_ref_rows(x, speeds, phases=None):
+    """fm_ref over the rows of a batch, row c with its own phasorSpeed and carried phase: (outputs, carried phases)."""
+    x = np.asarray(x, np.complex64)
+    speeds = np.asarray(speeds, np.float32).reshape(-1, 1)
+    phases = np.zeros(len(x), np.float32) if phases is None else np.asarray(phases, np.float32)
+    cp = fast_arctan2(x.imag, x.real)
+    prev = np.concatenate([phases.reshape(-1, 1), cp[:, :-1]], axis=1)
+    with np.errstate(all="ignore"):
+        d = (cp - prev).astype(np.float32)
+        d = np.where(d > PI, d - TWO_PI, np.where(d <= -PI, d + TWO_PI, d)).astype(np.float32)
+        out = (d / speeds).astype(np.float32)
+    return out, (cp[:, -1].copy() if x.shape[1] else phases.copy())
+
+
+def phasor_speeds(sample_rate, deviations):
+    """phasor_speed for an array of deviations."""
+    return (TWO_PI / (np.float32(sample_rate) / np.asarray(deviations, np.float32))).astype(np.float32)
+
+
+def am_candidates_of_mag(m):
+    """What the AM kernels' header allows for a row of magnitudes `m`: m - a in float32 for a = the float32 just below the
+    FP64 mean of m (math.fsum: the exact sum, rounded once) and the float32 just above it; one candidate where the mean is
+    a float32 itself (or not finite: a NaN or infinite mean poisons the row as it does in the reference).  -> [(a, m - a)]"""
+    m = np.asarray(m, np.float32)
+    with np.errstate(all="ignore"):
+        mu = math.fsum(m.tolist()) / len(m)
+        a = np.float32(mu)
+        if not np.isfinite(a) or float(a) == mu:
+            return [(a, (m - a).astype(np.float32))]
+        lo = a if float(a) < mu else np.nextafter(a, np.float32(-np.inf))
+        hi = np.nextafter(lo, np.float32(np.inf))
+        assert float(lo) < mu < float(hi)
+        return [(c, (m - c).astype(np.float32)) for c in (lo, hi)]
+
+
+def am_candidates(x):
+    """am_candidates_of_mag of a row of complex samples: |x| is VOLK's generic magnitude, bit for bit."""
+    return am_candidates_of_mag(am_mag(x))
+
+
+def am_row_ok(y, candidates):
+    """The whole row `y` has the bits of one candidate (the same mean subtracted from every sample)."""
+    return any(_same_bits(y, c) for _, c in candidates)
+
+
+def am_cancellation_row(n, seed):
+    """|x| = 4096 (1 + 2^-12 u), u uniform in [-1, 1], uniform argument: a mean of 4096 under samples that differ from it
+    by less than 1, so that m - avg keeps only the low bits of m and a mean that is off by one ulp (2^-12 below 4096) shows everywhere."""
+    rng = np.random.default_rng(seed)
+    r = 4096.0 * (1.0 + 2.0 ** -12 * rng.uniform(-1.0, 1.0, n))
+    return (r * np.exp(1j * rng.uniform(0.0, 2.0 * np.pi, n))).astype(np.complex64)
+
+
+def am_ref_f32_sequential(x):
+    """AMDemod::run with the mean accumulated in one float, sample after sample (what the reference's VOLK accumulator does)."""
+    m = am_mag(x)
+    avg = np.float32(np.cumsum(m, dtype=np.float32)[-1] / np.float32(len(m)))
+    return (m - avg).astype(np.float32), avg
+
+
+def am_ref_f32_tree(x, parts=1024):
+    """... with `parts` float partial sums (each over a contiguous share of the row, sample after sample) added in a pairwise tree."""
+    m = am_mag(x)
+    share = -(-len(m) // parts)
+    padded = np.zeros(parts * share, np.float32)
+    padded[:len(m)] = m
+    p = np.cumsum(padded.reshape(parts, share), axis=1, dtype=np.float32)[:, -1]
+    while len(p) > 1:
+        p = (p[0::2] + p[1::2]).astype(np.float32)
+    avg = np.float32(p[0] / np.float32(len(m)))
     return (m - avg).astype(np.float32), avg
 
 
@@ -252,3 +326,77 @@ def test_am_restatement():
     assert avg == np.float32(np.mean(m.astype(np.float64)))
     assert np.array_equal(y, m - avg)
     assert am_ref(x[:1])[0][0] == 0
+
+
+# ---- the restatements the GPU edge tests (tests/test_gpu_demod_edges.py) are built on ----------------------------------------
+def test_fm_ref_rows_is_fm_ref_row_by_row():
+    rng = np.random.default_rng(11)
+    x = (rng.standard_normal((5, 300)) + 1j * rng.standard_normal((5, 300))).astype(np.complex64)
+    x[3, 17] = complex(np.nan, 1.0)
+    x[4, 299] = complex(1.0, -np.inf)
+    devs = np.asarray([75_000.0, 12_500.0, 3_000.0, 1_001.0, 65_535.0], np.float32)
+    sp = phasor_speeds(250_000.0, devs)
+    ph = np.asarray([0.0, 1.5, -3.0, 0.25, np.nan], np.float32)
+    y, last = fm_ref_rows(x, sp, ph)
+    for c in range(5):
+        assert _same_bits([sp[c]], [phasor_speed(250_000.0, devs[c])])
+        want, p = fm_ref(x[c], sp[c], ph[c])
+        assert _same_bits(y[c], want) and _same_bits([last[c]], [p]), c
+    y0, last0 = fm_ref_rows(x[:, :0], sp, ph)
+    assert y0.shape == (5, 0) and _same_bits(last0, ph)
+    assert _same_bits(fm_ref_rows(x, sp)[0][:, 0], fm_ref_rows(x, sp, np.zeros(5))[0][:, 0])
+
+
+AM_CANCEL_N, AM_CANCEL_SEED = 1_000_003, 9
+
+
+def test_am_candidates_take_the_fp64_mean_and_refuse_float_accumulators():
+    """The candidate rule on the cancellation row: the FP64-mean restatement is one of the candidates; a mean accumulated in
+    float32 -- one running sum, or 1024 running sums added as a tree -- is neither.  A float running sum of this row stops
+    taking in the samples' offsets from 4096 once it has grown past 2^25, so its mean is off by about the mean of those
+    offsets, 1 / sqrt(3 n): of the order of one ulp of 4096 at n = 10^6, not many.  Which draws of the row a float
+    accumulator misses on is therefore chance: of seeds 0..15 at this count the running sum misses the candidates on nine
+    (by up to 3 ulp) and the 1024-partial tree on two (seeds 9 and 15, by 1 ulp); seed 9 is used because both miss there.
+    (A float accumulation that is pairwise all the way down stays within the candidates on this input at these sizes.)"""
+    x = am_cancellation_row(AM_CANCEL_N, AM_CANCEL_SEED)
+    m = am_mag(x)
+    assert 4094.99 < m.min() < 4095.01 and 4096.99 < m.max() < 4097.01
+    cands = am_candidates(x)
+    assert len(cands) == 2 and np.nextafter(cands[0][0], np.float32(np.inf)) == cands[1][0]
+    y, avg = am_ref(x)
+    assert am_row_ok(y, cands) and avg in (cands[0][0], cands[1][0])
+    assert np.abs(y).max() < 1.01                        # 12 of the 24 significant bits of m are gone in m - avg
+    for name, model in (("sequential", am_ref_f32_sequential), ("tree of 1024", am_ref_f32_tree)):
+        yf, af = model(x)
+        ulps = (float(af) - float(avg)) / float(np.spacing(avg))
+        print(f"{name}: mean {af!r}, {ulps:+.0f} ulp from the FP64 mean {avg!r}")
+        assert not am_row_ok(yf, cands), name
+        assert af not in (cands[0][0], cands[1][0]), name
+
+
+def test_am_candidates_edges():
+    rng = np.random.default_rng(5)
+    x = (rng.standard_normal(4097) + 1j * rng.standard_normal(4097)).astype(np.complex64)
+    # unit noise: the FP64 restatement is a candidate (at every count the GPU tests use below the partials cap)
+    for n in (1, 2, 7, 8, 9, 2047, 2048, 2049, 4097):
+        y, avg = am_ref(x[:n])
+        cands = am_candidates(x[:n])
+        assert am_row_ok(y, cands) and any(_same_bits([avg], [a]) for a, _ in cands), n
+    # one sample, or a mean that is a float32: one candidate
+    assert len(am_candidates(x[:1])) == 1 and not np.any(am_candidates(x[:1])[0][1])
+    (a, c), = am_candidates(np.asarray([3 + 4j, 3 + 4j, 6 + 8j, 0], np.complex64))
+    assert a == np.float32(5) and np.array_equal(c, np.asarray([0, 0, 5, -5], np.float32))
+    # a candidate differs from the other in about every sample, and from a row with a sample off by an ulp
+    lo, hi = am_candidates(x)
+    assert not am_row_ok(np.where(np.arange(4097) < 2000, lo[1], hi[1]), [lo, hi]), "one mean for the whole row"
+    off = lo[1].copy()
+    off[4096] = np.nextafter(off[4096], np.float32(9))
+    assert not am_row_ok(off, [lo, hi])
+    # non-finite: the mean is NaN or infinite, and the row is the reference's
+    for bad in (complex(np.nan, 1), complex(1, np.inf), complex(-np.inf, 0)):
+        xb = x[:100].copy()
+        xb[37] = bad
+        (a, c), = am_candidates(xb)
+        with np.errstate(all="ignore"):
+            assert not np.isfinite(a) and _same_bits(c, am_ref(xb)[0])
+        assert np.all(np.isnan(c)) if np.isnan(a) else (np.isnan(c[37]) and np.all(c[np.arange(100) != 37] == -np.inf))
