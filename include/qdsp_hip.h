@@ -479,6 +479,49 @@ int qdsp_hip_agc_process_batch_dev(void* h, const void* d_in, int64_t count, int
 int qdsp_hip_agc_reset(void* h);
 void qdsp_hip_agc_destroy(void* h);
 
+/* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
+/* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
+ * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the
+ * reference (which has no PLL and no loop over samples but the FM phase), as three launches on one stream:
+ *   m = FloatFMDemod(in), bit-identical to QDSP_HIP_DEMOD_FM with the same phase (fm_demod_kernel).
+ *   f[i] = sum_k pilot_taps[k] m[i - (ntaps - 1) + k]: FIR<float>, the tap convention and the (ntaps - 1)-sample history of
+ *        qdsp_hip_fir_f32, the history 0 after create / reset (pilot_fir_kernel).  Each output is the FP32 chain
+ *        acc = fmaf(taps[k], m[..], acc) for k = 0 .. ntaps - 1 from +0.0f: its bits depend on the taps and the ntaps samples under
+ *        them alone, not on where the stream is cut into calls, on the channel index or count, or on the alignment of the rows.
+ *        The reference's taps are BlackmanBandpassWindow(1000, 1000, 19000, sampleRate); ntaps <= 4096, shared by all channels.
+ *   level: AGC's update exactly as stated for qdsp_hip_agc_* above, on f, with cfr = 20.0f / sample_rate (demodulator.h:219):
+ *        the decay in dB by cfr * count, then the maximum of the call's f under `x > level`.  0 after create / reset.
+ *   p = f * (1.0f / level);  d = p * p;  s = m * d;  out = {m + s, m - s}, every operation rounded to float (stereo_mix_kernel).
+ *        Bit-identical to the reference's VOLK lines given m, f and the level; AGC's corner cases are kept (a level of 0 with no
+ *        positive f gives p = f * inf; an Inf pins the level; a NaN never raises it).  As in the reference, the filter's delay is
+ *        not compensated: m is not delayed against p.
+ * A NaN input sample at i makes m[i] and m[i + 1] NaN, hence the outputs i .. i + ntaps of that channel and no others.
+ * set_fm(chan, sample_rate, deviation): phasorSpeed as qdsp_hip_demod_set_fm, and cfr; default sample_rate = deviation = 1; a
+ * sample_rate that is not finite and positive is QDSP_HIP_EINVAL.  `chan` -1 = every channel (set_fm, set_phase, set_level).
+ * set_pilot_taps replaces the taps of all channels and zeroes the history -- a departure: FIR<float>::updateWindow keeps the
+ * old samples -- and leaves phase and level alone.  pilot_dev: the device rows of f of the last call, `*stride` floats apart,
+ * 16-byte aligned, valid until the next call on this handle (NULL before the first); read them on the stream of that call.
+ * process / process_ex (nchan 1): host pointers / link codes as for every *_process_ex, `count` <= max_block where a side is on
+ * the host (else QDSP_HIP_ESIZE).  process_dev: the nchan rows back to back (strides = count).  Device pointers 8-byte aligned;
+ * 16-byte aligned rows with even strides take the vector loads and stores.  count == 0 is a no-op.  QDSP_HIP_EINVAL: ntaps < 1
+ * or > 4096, nchan > 65535, spans of input and output that overlap.  m and f live in library-owned rows that grow to the largest
+ * call seen (a call larger than max_block and every call before it synchronises the device once).  get_* synchronise the device. */
+int qdsp_hip_stereo_fm_create(void** h, int device, int nchan, const float* pilot_taps, int ntaps, int max_block);
+int qdsp_hip_stereo_fm_set_fm(void* h, int chan, float sample_rate, float deviation);
+int qdsp_hip_stereo_fm_set_pilot_taps(void* h, const float* pilot_taps, int ntaps);
+int qdsp_hip_stereo_fm_process(void* h, const float* in_iq, int count, float* out_lr);
+int qdsp_hip_stereo_fm_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_stereo_fm_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_stereo_fm_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                         int64_t out_stride, void* hip_stream);
+int qdsp_hip_stereo_fm_get_phase(void* h, int chan, float* phase);
+int qdsp_hip_stereo_fm_set_phase(void* h, int chan, float phase);
+int qdsp_hip_stereo_fm_get_level(void* h, int chan, float* level);
+int qdsp_hip_stereo_fm_set_level(void* h, int chan, float level);
+int qdsp_hip_stereo_fm_pilot_dev(void* h, void** d_pilot, int64_t* stride);
+int qdsp_hip_stereo_fm_reset(void* h);
+void qdsp_hip_stereo_fm_destroy(void* h);
+
 /* ---- synthetic IQ source (measurement harness) ------------------------------ */
 /* Counter-based uniform [-1,1) per float component, generated on device so benchmarks are
  * HBM->HBM.  Bit-identical to oracle_synth_iq() for the same (first_sample, seed). */

@@ -210,6 +210,21 @@ def load():
     sig("qdsp_hip_agc_set", i32, vp, i32, C.c_float, C.c_float)
     sig("qdsp_hip_agc_get_level", i32, vp, i32, fp)
     sig("qdsp_hip_agc_set_level", i32, vp, i32, C.c_float)
+    p = "qdsp_hip_stereo_fm"
+    sig(p + "_create", i32, pvp, i32, i32, fp, i32, i32)
+    sig(p + "_set_fm", i32, vp, i32, C.c_float, C.c_float)
+    sig(p + "_set_pilot_taps", i32, vp, fp, i32)
+    sig(p + "_process", i32, vp, vp, i32, vp)
+    sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+    sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp)
+    sig(p + "_get_phase", i32, vp, i32, fp)
+    sig(p + "_set_phase", i32, vp, i32, C.c_float)
+    sig(p + "_get_level", i32, vp, i32, fp)
+    sig(p + "_set_level", i32, vp, i32, C.c_float)
+    sig(p + "_pilot_dev", i32, vp, pvp, C.POINTER(i64))
+    sig(p + "_reset", i32, vp)
+    sig(p + "_destroy", None, vp)
     sig("qdsp_hip_set_done_event", i32, vp, vp)
     sig("qdsp_hip_event_create", i32, i32, pvp)
     sig("qdsp_hip_event_destroy", i32, vp)

@@ -370,6 +370,11 @@ int demod_process_ex(Demod* d, const void* in, int in_link, int count, void* out
 bool chan_ok(const Demod* d, int chan) { return chan >= 0 && chan < d->nchan; }
 }  // namespace
 
+// fm_demod_kernel with float rows out, for a caller that keeps its own phase slots (stereo_fm.hip): the launch alone
+void launch_fm_mono(const qk::FmArgs& a, int tiles, int nchan, hipStream_t s) {
+    hipLaunchKernelGGL((qk::fm_demod_kernel<false>), dim3((unsigned)tiles, (unsigned)nchan), dim3(qk::kDemodNT), 0, s, a);
+}
+
 int demod_time(Demod* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
     if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));

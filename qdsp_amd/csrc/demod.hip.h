@@ -125,5 +125,6 @@ inline Demod* as_demod(void* h) {
     return (d && d->magic == kDemodMagic) ? d : nullptr;
 }
 int demod_time(Demod* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
+void launch_fm_mono(const qk::FmArgs& a, int tiles, int nchan, hipStream_t s);
 
 }  // namespace qh

@@ -9,19 +9,6 @@ namespace {
 template <int KIND> struct Red { using type = double; };    // Squelch: FP64 sum of |x|
 template <> struct Red<kLevelAgc> { using type = float; };  // AGC: maximum of x
 
-// a workgroup's maximum of one float per lane under the reference's predicate (block_sum's tree)
-__device__ __forceinline__ float block_max(float m, float* red) {
-    const int t = threadIdx.x;
-    red[t] = m;
-    __syncthreads();
-#pragma unroll
-    for (int w = kDemodNT / 2; w > 0; w >>= 1) {
-        if (t < w && red[t + w] > red[t]) red[t] = red[t + w];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // the n samples a lane holds, folded into its accumulator: sum of |x| (Squelch) / maximum (AGC: `if (x > level) level = x`)
 template <int KIND, int NC> __device__ __forceinline__ void fold_lane(const float (&x)[kDemodSpl * NC], int n, typename Red<KIND>::type& acc) {
 #pragma unroll
@@ -38,15 +25,6 @@ __device__ __forceinline__ bool squelch_open(double sum, long long count, float 
 #pragma clang fp contract(off)
     const float mean = (float)(sum / (double)count);
     return 10.0f * log10f(mean) >= level;
-}
-
-// AGC::run, the decay and the peak (processing.h:123-127): the inner expression in float, pow(10, float) in double
-__device__ __forceinline__ float agc_level(float level, float cfr, long long count, float peak) {
-#pragma clang fp contract(off)
-    const float e = ((10.0f * log10f(level)) - (cfr * (float)count)) / 10.0f;
-    level = (float)pow(10.0, (double)e);
-    if (peak > level) level = peak;
-    return level;
 }
 
 // The call's scalar of channel c from the workgroup's reduced value: Squelch 1.0f (open) or 0.0f, AGC 1.0f / level.  Every lane

@@ -36,6 +36,29 @@ struct LevelArgs {
     int vec;                    // 1: every row 16-byte aligned
 };
 
+// ---- device helpers shared by level.hip and stereo_fm.hip ----
+// a workgroup's maximum of one float per lane under the reference's predicate (block_sum's tree)
+__device__ __forceinline__ float block_max(float m, float* red) {
+    const int t = threadIdx.x;
+    red[t] = m;
+    __syncthreads();
+#pragma unroll
+    for (int w = kDemodNT / 2; w > 0; w >>= 1) {
+        if (t < w && red[t + w] > red[t]) red[t] = red[t + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// AGC::run, the decay and the peak (processing.h:123-127): the inner expression in float, pow(10, float) in double
+__device__ __forceinline__ float agc_level(float level, float cfr, long long count, float peak) {
+#pragma clang fp contract(off)
+    const float e = ((10.0f * log10f(level)) - (cfr * (float)count)) / 10.0f;
+    level = (float)pow(10.0, (double)e);
+    if (peak > level) level = peak;
+    return level;
+}
+
 }  // namespace qk
 
 namespace qh {

@@ -8,8 +8,9 @@
 //                           init() computes it.
 //   AMDemod                 qdsp_hip_demod_* (AM): |x| minus the mean of the call, the mean summed in FP64
 //   SSBDemod                qdsp_hip_ssb_cf32_*: the xlator's NCO with the reference's phaseDelta, real part out
-// The blocks of the reference header built around serial loops (StereoFMDemod's pilot PLL, MSK / PSK: AGC, Costas loop,
-// clock recovery) are not provided.
+// StereoFMDemod is in dsp/stereo_demod.h: the reference's block has no PLL -- FloatFMDemod, a FIR<float> on the 19 kHz pilot, AGC
+// and three element-wise lines -- and is one handle here (qdsp_hip_stereo_fm_*).  The blocks of the reference header built around
+// serial loops (MSK / PSK: complex AGC, Costas loop, clock recovery) are not provided.
 #pragma once
 #include <cmath>
 

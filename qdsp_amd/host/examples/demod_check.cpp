@@ -17,6 +17,9 @@
 //   demod_check agc <dev|host> <in.cf32> <out> <block> <offset> <inSR> <outSR> <bw> <fall_rate>
 //                   source -> VFO -> AMDemod -> AGC (dsp/processing.h) -> sink; host: both links into and out of the AMDemod on
 //                   the host buffers.
+//   demod_check sfm <in.cf32> <out> <block> <sampleRate> <deviation>
+//                   source -> StereoFMDemod (dsp/stereo_demod.h) -> sink: the file is the demodulator's own input, read in blocks of
+//                   <block> samples, one run() each; stereo_t out.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -32,6 +35,7 @@
 #include <dsp/processing.h>
 #include <dsp/sink.h>
 #include <dsp/source.h>
+#include <dsp/stereo_demod.h>
 #include <dsp/vfo.h>
 
 using namespace dsp;
@@ -109,9 +113,41 @@ static int runGraph(const char* inPath, const char* outPath, int block, float of
     return 0;
 }
 
+// source -> StereoFMDemod -> sink, every block of the file one run()
+static int runStereo(const char* inPath, const char* outPath, int block, float sampleRate, float deviation) {
+    Feed feed;
+    feed.data = readAll(inPath);
+    feed.block = block;
+    const long nblocks = (long)((feed.data.size() + block - 1) / block);
+    HandlerSource<complex_t> src(Feed::pull, &feed);
+    StereoFMDemod demod(&src.out, sampleRate, deviation);
+    Writer<stereo_t> w;
+    w.file.open(outPath, std::ios::binary);
+    HandlerSink<stereo_t> sink(&demod.out, Writer<stereo_t>::push, &w);
+    sink.start();
+    demod.start();
+    src.start();
+    const auto t0 = std::chrono::steady_clock::now();
+    while (w.blocks.load() < nblocks) {
+        std::this_thread::sleep_for(std::chrono::milliseconds(1));
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) { fprintf(stderr, "graph timed out\n"); return 3; }
+        if (hipBlockErrors() > 0) { fprintf(stderr, "a block failed\n"); return 4; }
+    }
+    src.stop();
+    demod.stop();
+    sink.stop();
+    w.file.close();
+    printf("graph ok: %zu in, %ld out, %ld blocks, %d pilot taps\n", feed.data.size(), w.samples.load(), nblocks, demod.getPilotTapCount());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
     const std::string mode = argv[1];
+    if (mode == "sfm") {
+        if (argc < 7) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
+        return runStereo(argv[2], argv[3], atoi(argv[4]), (float)atof(argv[5]), (float)atof(argv[6]));
+    }
     if (mode == "vfo" && argc >= 9) {
         const float off = (float)atof(argv[5]), inSR = (float)atof(argv[6]), outSR = (float)atof(argv[7]), bw = (float)atof(argv[8]);
         return runGraph<complex_t>(argv[2], argv[3], atoi(argv[4]), off, inSR, outSR, bw, false,

@@ -814,3 +814,148 @@ class Agc(_Level):
 
 
 __all__ += ["Squelch", "Agc"]
+
+
+def stereo_pilot_taps(sample_rate: float) -> np.ndarray:
+    """StereoFMDemod's pilot filter (src/dsp/demodulator.h:217): BlackmanBandpassWindow(1000, 1000, 19000, sampleRate) with the
+    reference's tap count, every step in float in the reference's order (src/dsp/window.h:105-140) with glibc's sinf / cosf, as
+    the C++ mirror's dsp/window.h computes it (tests/test_stereo_fm_cpu.py pins both to the CPU oracle bit for bit)."""
+    f32, m = np.float32, _libm()
+    sinf = lambda v: f32(m.sinf(C.c_float(v)))    # noqa: E731
+    cosf = lambda v: f32(m.cosf(C.c_float(v)))    # noqa: E731
+    fs, cutoff, trans, offset = f32(sample_rate), f32(1000.0), f32(1000.0), f32(19000.0)
+    n = int(f32(4.0) / f32(trans / fs))
+    n = max(n, 4)
+    n += 1 if n % 2 == 0 else 0
+    fc = min(f32(cutoff / fs), f32(1.0))
+    tc = f32(n)
+    window = f32(f32(f32(0.42) - f32(f32(0.5) * cosf(f32(f32(f32(2.0) * FL_M_PI) / tc)))) + f32(f32(0.8) * cosf(f32(f32(f32(4.0) * FL_M_PI) / tc))))
+    taps, total = np.zeros(n, f32), f32(0.0)
+    for i in range(n):
+        d = f32(f32(i) - f32(tc / f32(2.0)))
+        with np.errstate(all="ignore"):
+            v = f32(f32(sinf(f32(f32(f32(f32(2.0) * FL_M_PI) * fc) * d)) / d) * window)
+        taps[i] = v
+        total = f32(total + v)
+    shift = f32(f32(f32(2.0) * f32(offset / fs)) * FL_M_PI)
+    for i in range(n):
+        taps[i] = f32(f32(taps[i] * cosf(f32(shift * f32(i)))) * f32(1.0)) / total
+    return taps
+
+
+class StereoFmDemod(_Demod):
+    """dsp::StereoFMDemod (src/dsp/demodulator.h:189-330): FloatFMDemod, the 19 kHz pilot FIR, AGC(20, sampleRate) and the
+    matrix {m + m p^2, m - m p^2}; `nchan` channels per call, each with its own deviation, phase, filter history and level.
+    `pilot_taps` (shared by all channels) default to the reference's for `sample_rate` (a scalar then)."""
+
+    _prefix = "qdsp_hip_stereo_fm"
+    _stereo = True
+
+    def __init__(self, sample_rate, deviation, nchan: int = 1, pilot_taps=None, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        self._count = 0
+        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
+        devs = np.broadcast_to(np.asarray(deviation, dtype=np.float32), (self.nchan,))
+        if pilot_taps is None:
+            assert np.all(rates == rates[0]), "one pilot filter for all channels: pass pilot_taps"
+            pilot_taps = stereo_pilot_taps(float(rates[0]))
+        t, tp = _taps_ptr(pilot_taps)
+        self.ntaps = int(t.size)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, tp, self.ntaps, max_block), "qdsp_hip_stereo_fm_create")
+        for c in range(self.nchan):
+            self.set_fm(float(rates[c]), float(devs[c]), c)
+
+    def process(self, x, out=None):
+        y = super().process(x, out)
+        if not _is_torch(x):
+            self._count = len(y)
+        return y
+
+    def _process_dev(self, x, out=None):
+        y = super()._process_dev(x, out)
+        self._count = x.numel() // self.nchan
+        return y
+
+    def process_batch(self, x, out=None, count: int = None):
+        """Channel c = row c of the 2-D complex64 tensor `x` (rows may be padded); returns (nchan, count, 2) float32."""
+        import torch
+
+        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.complex64 and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        if out is None:
+            out = torch.empty((self.nchan, max(n, 1), 2), dtype=torch.float32, device=x.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == 2
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0) // 2, stream),
+                   "qdsp_hip_stereo_fm_process_batch_dev")
+        self._count = n
+        return out[:, :n]
+
+    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
+        rc = super().process_ex(x, in_link, count, out, out_link)
+        self._count = int(count)
+        return rc
+
+    def set_fm(self, sample_rate: float, deviation: float, chan: int = -1):
+        capi.check(self._fn("set_fm")(self._h, int(chan), sample_rate, deviation), "qdsp_hip_stereo_fm_set_fm")
+
+    def set_pilot_taps(self, taps):
+        """New taps for all channels; the filter history is zeroed, phase and level stay."""
+        t, tp = _taps_ptr(taps)
+        capi.check(self._fn("set_pilot_taps")(self._h, tp, int(t.size)), "qdsp_hip_stereo_fm_set_pilot_taps")
+        self.ntaps = int(t.size)
+
+    def get_phase(self, chan: int = 0):
+        v = C.c_float()
+        capi.check(self._fn("get_phase")(self._h, int(chan), C.byref(v)))
+        return np.float32(v.value)
+
+    def set_phase(self, phase: float, chan: int = -1):
+        capi.check(self._fn("set_phase")(self._h, int(chan), phase))
+
+    def level(self, chan: int = 0):
+        """The carried AGC level (synchronises the device)."""
+        v = C.c_float()
+        capi.check(self._fn("get_level")(self._h, int(chan), C.byref(v)))
+        return np.float32(v.value)
+
+    def set_level(self, level: float, chan: int = -1):
+        capi.check(self._fn("set_level")(self._h, int(chan), level))
+
+    def pilot_ptr(self):
+        """(device pointer, row stride in floats) of the library's own rows of the last call's filtered pilot f; the next
+        call overwrites them (qdsp_hip_stereo_fm_pilot_dev)."""
+        p, stride = C.c_void_p(), C.c_int64()
+        capi.check(self._fn("pilot_dev")(self._h, C.byref(p), C.byref(stride)), "qdsp_hip_stereo_fm_pilot_dev")
+        return p.value or 0, int(stride.value)
+
+    def pilot(self):
+        """The last call's filtered pilot f as a new (nchan, count) float32 tensor (synchronises the device)."""
+        import torch
+
+        p, stride = self.pilot_ptr()
+        rows = torch.empty((self.nchan, max(stride, 1)), dtype=torch.float32, device=f"cuda:{self.device}")
+        if p and self._count:
+            torch.cuda.synchronize(self.device)
+            capi.check(self._L.qdsp_hip_memcpy_d2d(self.device, rows.data_ptr(), p, self.nchan * stride * 4), "qdsp_hip_memcpy_d2d")
+        return rows[:, :self._count if p else 0]
+
+    def reset(self):
+        capi.check(self._fn("reset")(self._h))
+        self._count = 0
+
+    def time_dev(self, x, out, iters: int) -> float:
+        """Mean ms per call of `iters` back-to-back process_dev calls over the nchan rows of `x` (qdsp_hip_time_process_dev)."""
+        import torch
+
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ms = C.c_float()
+        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.numel() // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
+        capi.check(rc, "qdsp_hip_time_process_dev")
+        self._count = x.numel() // self.nchan
+        return float(ms.value)
+
+
+__all__ += ["StereoFmDemod", "stereo_pilot_taps"]
