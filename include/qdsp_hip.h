@@ -479,6 +479,45 @@ int qdsp_hip_agc_process_batch_dev(void* h, const void* d_in, int64_t count, int
 int qdsp_hip_agc_reset(void* h);
 void qdsp_hip_agc_destroy(void* h);
 
+/* ---- feed-forward AGC : FeedForwardAGC<T>, src/dsp/processing.h:147-233 --------------------- */
+/* A sliding-window peak normaliser with no recurrence; nchan channel-major rows per call, strides in samples.  With the stream of
+ * all samples ever handed to a row, x[0], x[1], ..., and the window W (`window`, 1 .. 4096; the reference has 1024):
+ *   y[p] = x[p] / level[p],   level[p] = max(1e-4f, max over j in [0, W) of a(x[p + j]))
+ *   QDSP_HIP_FFAGC_REAL     float rows:     a(v) = fabsf(v), y = v / level
+ *   QDSP_HIP_FFAGC_COMPLEX  complex_t rows: a(v) = r + 0.4f * r with r = fabsf(v.re), product and sum each rounded to float --
+ *        the reference's fastAmplitude (types.h:58-63) takes both of its magnitudes from re, and that is kept: im never enters
+ *        the level.  y = {re / level, im / level}, two IEEE divisions.
+ * The maximum runs under the reference's `val > level` from 1e-4f: a NaN never wins (it is a NaN output at its own index only);
+ * +Inf wins and makes the W outputs whose window holds it 0 (NaN at the Inf itself).  Bit-identical to the reference loop.
+ * y[p] needs x[p + W - 1]: the block lags by W - 1 samples.  The handle keeps the last `fill` <= W - 1 inputs not yet output
+ * (every row the same number), on the device, double-buffered.  A call of `count` inputs per row emits
+ * out = max(0, fill + count - (W - 1)) outputs per row -- the next `out` stream positions -- and leaves fill + count - out; a call
+ * that emits nothing still takes its inputs.  The outputs depend on the stream alone, not on where the calls cut it.
+ * process / process_ex (nchan 1; link codes as for every *_process_ex; `count` <= max_block where a side is on the host, else
+ * QDSP_HIP_ESIZE) and the *_dev entry points return the number of outputs per row (>= 0) or an error.  process_dev: the nchan
+ * input rows `count` apart, the output rows out_size(count) apart.  process_batch_dev: in_stride >= count, out_stride >= out.
+ * Pointers: 4-byte (REAL) / 8-byte (COMPLEX) aligned; 16-byte aligned output rows whose stride is a whole number of 16-byte units
+ * take 16-byte stores, any others narrower ones, with the same bits.  Input and output may not overlap: any overlap of the two row
+ * spans is QDSP_HIP_EINVAL (an output depends on the inputs after its own).
+ * out_size: what the next call of `count` would emit.  get_history: the `fill` samples held for `chan`, oldest first (`hist` holds
+ * window - 1 samples).  set_history: `fill` samples for row `chan` (-1: the same for every row) and the handle's fill; set every
+ * row when the fill changes.  get_history / set_history / reset synchronise the device; reset empties the history. */
+#define QDSP_HIP_FFAGC_REAL 0
+#define QDSP_HIP_FFAGC_COMPLEX 1
+int qdsp_hip_ffagc_create(void** h, int device, int kind, int nchan, int max_block, int window);
+int qdsp_hip_ffagc_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_ffagc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int64_t qdsp_hip_ffagc_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int64_t qdsp_hip_ffagc_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                         int64_t out_stride, void* hip_stream);
+int64_t qdsp_hip_ffagc_out_size(void* h, int64_t count);
+int qdsp_hip_ffagc_window(void* h);
+int qdsp_hip_ffagc_fill(void* h);
+int qdsp_hip_ffagc_get_history(void* h, int chan, float* hist);
+int qdsp_hip_ffagc_set_history(void* h, int chan, const float* hist, int fill);
+int qdsp_hip_ffagc_reset(void* h);
+void qdsp_hip_ffagc_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

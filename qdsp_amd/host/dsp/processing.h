@@ -1,5 +1,5 @@
-// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch and dsp::AGC, HIP-backed (the reference's
-// other blocks in this header -- FeedForwardAGC, ComplexAGC, packer ... -- are not provided).
+// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch, dsp::AGC and dsp::FeedForwardAGC<T>, HIP-backed (the
+// reference's other blocks in this header -- ComplexAGC, packer ... -- are not provided).
 //
 // Drop-in for src/dsp/processing.h:10-81.  init()/setSampleRate()/setFrequency() compute
 // phaseDelta exactly as the reference does -- theta = (freq/sampleRate) * 2.0f * FL_M_PI in
@@ -274,6 +274,78 @@ private:
     float _fallRate = 0.0f;
     float _sampleRate = 1.0f;
     stream<float>* _in = nullptr;
+    void* handle = nullptr;
+    detail::done_events done;
+};
+
+// FeedForwardAGC<T> (src/dsp/processing.h:147-233), T = float or complex_t: same constructors, init(), setInput() and `out`.  The
+// window is the reference's 1024 samples; the samples not yet output live on the device (qdsp_hip_ffagc_*).  run() publishes exactly
+// the samples the call produced -- count - 1023 on the first emitting call, count afterwards -- and does not swap while the history
+// fills (the reference publishes `count` there, of which only toProcess are written).
+template <class T>
+class FeedForwardAGC : public generic_block<FeedForwardAGC<T>> {
+    static_assert(std::is_same<T, float>::value || std::is_same<T, complex_t>::value, "FeedForwardAGC: float or complex_t");
+    using base = generic_block<FeedForwardAGC<T>>;
+
+public:
+    FeedForwardAGC() {}
+
+    FeedForwardAGC(stream<T>* in) { init(in); }
+
+    ~FeedForwardAGC() {
+        const bool live = base::running;
+        base::stop();
+        if (live && _in) { _in->releaseConsumer(); }
+        if (handle) { qdsp_hip_ffagc_destroy(handle); }
+    }
+
+    void init(stream<T>* in) {
+        _in = in;
+        const int kind = std::is_same<T, complex_t>::value ? QDSP_HIP_FFAGC_COMPLEX : QDSP_HIP_FFAGC_REAL;
+        const int rc = qdsp_hip_ffagc_create(&handle, detail::hipDeviceForBlocks(), kind, 1, STREAM_BUFFER_SIZE, sampleCount);
+        if (rc != 0) { handle = nullptr; detail::hipBlockFail("FeedForwardAGC::init", rc); }
+        base::registerInput(_in);
+        base::registerOutput(&out);
+        _in->claimConsumer(handle != nullptr, true);
+    }
+
+    void setInput(stream<T>* in) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        base::unregisterInput(_in);
+        _in->releaseConsumer();
+        _in = in;
+        _in->claimConsumer(handle != nullptr, true);
+        base::registerInput(_in);
+        base::tempStart();
+    }
+
+    int run() override {
+        const int count = _in->read();
+        if (count < 0) { return -1; }
+        if (!handle) { return -1; }
+        const bool emits = qdsp_hip_ffagc_out_size(handle, count) > 0;
+        const bool inDev = _in->readOnDevice;
+        const bool outDev = emits && out.consumerTakesDevice && out.ensureDevice(detail::hipDeviceForBlocks());
+        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
+        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
+        void* evt = nullptr;
+        // (a call that only fills the history writes no output: nothing to hand over, no event to arm)
+        const int outLink = outDev ? out.linkOut(true) : (emits ? done.arm(handle, evt) : QDSP_HIP_LINK_HOST);
+        const int outCount = qdsp_hip_ffagc_process_ex(handle, src, _in->linkIn(), count, dst, outLink);
+        _in->flush();
+        if (outCount < 0) { return detail::hipBlockFail("FeedForwardAGC::run", outCount); }
+        if (outCount == 0) { return count; }
+        out.markWritten(outLink, evt);
+        if (!out.swap(outCount)) { return -1; }
+        return outCount;
+    }
+
+    stream<T> out;
+
+private:
+    int sampleCount = 1024;
+    stream<T>* _in = nullptr;
     void* handle = nullptr;
     detail::done_events done;
 };

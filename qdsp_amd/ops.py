@@ -689,12 +689,38 @@ class Deemp(_Op):
 __all__ += ["Deemp"]
 
 
-class _Level(_Op):
+class _RowOp(_Op):
+    """What the handles over `nchan` channel rows share: the block-graph entry point, the completion event, reset and timing."""
+
+    nchan = 1
+
+    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
+        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
+        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
+
+    def set_done_event(self, ev: int):
+        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
+
+    def reset(self):
+        capi.check(self._fn("reset")(self._h))
+
+    def time_dev(self, x, out, iters: int) -> float:
+        """Mean ms per launch of `iters` back-to-back process_dev calls over the nchan rows of `x`, back to back
+        (qdsp_hip_time_process_dev)."""
+        import torch
+
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ms = C.c_float()
+        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.numel() // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
+        capi.check(rc, "qdsp_hip_time_process_dev")
+        return float(ms.value)
+
+
+class _Level(_RowOp):
     """One reduction over a call, then one pass over it, per channel (include/qdsp_hip.h: level blocks).  numpy input: the host
     entry point (one channel); a 1-D torch tensor: *_process_dev; a 2-D one: one row per channel (`process_batch`)."""
 
     _np, _tt = np.float32, "float32"
-    nchan = 1
 
     def process(self, x, out=None):
         if _is_torch(x):
@@ -735,27 +761,6 @@ class _Level(_Op):
         capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), stream),
                    self._prefix + "_process_batch_dev")
         return out[:, :n]
-
-    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
-        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
-        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
-
-    def set_done_event(self, ev: int):
-        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
-
-    def reset(self):
-        capi.check(self._fn("reset")(self._h))
-
-    def time_dev(self, x, out, iters: int) -> float:
-        """Mean ms per launch of `iters` back-to-back process_dev calls over the nchan rows of `x`, back to back
-        (qdsp_hip_time_process_dev)."""
-        import torch
-
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ms = C.c_float()
-        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.numel() // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
-        capi.check(rc, "qdsp_hip_time_process_dev")
-        return float(ms.value)
 
 
 class Squelch(_Level):
@@ -959,3 +964,96 @@ class StereoFmDemod(_Demod):
 
 
 __all__ += ["StereoFmDemod", "stereo_pilot_taps"]
+
+
+class FeedForwardAgc(_RowOp):
+    """dsp::FeedForwardAGC<T> (src/dsp/processing.h:147-233): every sample divided by the peak of the `window` samples from it on
+    (a sliding-window maximum, floor 1e-4).  `kind_or_dtype`: 0 / "real" / float32 for float rows, 1 / "complex" / complex64 for
+    complex_t rows (the level follows |re| alone, as the reference's fastAmplitude does).  The output lags the input by
+    window - 1 samples: a call of n samples returns `out_size(n)` outputs, none at all while the history fills.  `nchan` rows per
+    launch share one fill."""
+
+    _prefix = "qdsp_hip_ffagc"
+    REAL, COMPLEX = 0, 1
+
+    def __init__(self, kind_or_dtype=1, nchan: int = 1, device: int = 0, max_block: int = 1_000_000, window: int = 1024):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        self.kind = self._kind_of(kind_or_dtype)
+        self._np, self._tt = (np.complex64, "complex64") if self.kind == self.COMPLEX else (np.float32, "float32")
+        self.window = int(window)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, max_block, self.window), "qdsp_hip_ffagc_create")
+
+    @classmethod
+    def _kind_of(cls, k) -> int:
+        if isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+            return int(k)
+        if isinstance(k, str) and k in ("real", "complex"):
+            return cls.COMPLEX if k == "complex" else cls.REAL
+        name = str(k).rsplit(".", 1)[-1]           # numpy and torch dtypes and scalar types alike
+        for want, kind in (("complex64", cls.COMPLEX), ("float32", cls.REAL)):
+            if want in name:
+                return kind
+        raise ValueError(f"FeedForwardAgc: float32 or complex64 rows, not {k!r}")
+
+    def out_size(self, n: int) -> int:
+        """What the next call of `n` samples (per row) would emit."""
+        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), "qdsp_hip_ffagc_out_size"))
+
+    def fill(self) -> int:
+        """The samples taken in and not yet output (per row)."""
+        return capi.check(self._fn("fill")(self._h), "qdsp_hip_ffagc_fill")
+
+    def get_history(self, chan: int = 0) -> np.ndarray:
+        h = np.zeros(max(self.window - 1, 1), dtype=self._np)
+        capi.check(self._fn("get_history")(self._h, int(chan), h.ctypes.data), "qdsp_hip_ffagc_get_history")
+        return h[:self.fill()]
+
+    def set_history(self, hist, chan: int = -1):
+        h = np.ascontiguousarray(hist, dtype=self._np)
+        capi.check(self._fn("set_history")(self._h, int(chan), h.ctypes.data, h.size), "qdsp_hip_ffagc_set_history")
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=self._np)
+        assert a.ndim == 1, a.shape
+        y = np.empty(max(self.out_size(a.size), 1), dtype=self._np)
+        no = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:no]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
+        n = x.numel()
+        if out is None:
+            out = torch.empty(max(self.out_size(n), 1), dtype=dt, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= self.out_size(n)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        no = capi.check(int(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream)), self._prefix + "_process_dev")
+        return out[:no]
+
+    def process_batch(self, x, out=None, count: int = None):
+        """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count); returns the (nchan, out_size(count))
+        view of `out`.  `out` may not overlap `x`."""
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        no = self.out_size(n)
+        if out is None:
+            out = torch.empty((self.nchan, max(no, 1)), dtype=dt, device=x.device)
+        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= no and out.stride(1) == 1
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), stream)
+        no = capi.check(int(rc), self._prefix + "_process_batch_dev")
+        return out[:, :no]
+
+
+__all__ += ["FeedForwardAgc"]
