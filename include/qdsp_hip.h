@@ -518,6 +518,37 @@ int qdsp_hip_ffagc_set_history(void* h, int chan, const float* hist, int fill);
 int qdsp_hip_ffagc_reset(void* h);
 void qdsp_hip_ffagc_destroy(void* h);
 
+/* ---- complex AGC : ComplexAGC, src/dsp/processing.h:235-298 ---------------------------------- */
+/* The per-sample feedback AGC on complex_t rows; nchan channel-major rows per call, strides in samples, each channel with its own
+ * set point, maximum gain, rate and gain (FP64, on the device, 1 at creation):
+ *   out[i] = in[i] * g;   g += (set_point - |out[i]|) * rate;   if (g > max_gain) g = max_gain
+ * While g >= 0 a sample is the map g -> min(a g + b, c), a = 1 - rate |in[i]|, b = set_point rate, c = max_gain, and these maps
+ * compose associatively: a row is run as an FP64 prefix scan and every output is rounded to float once.  The result is the
+ * exact recurrence of the float parameters to within |y - x g| <= 0.5 ulp(x g) + |x| 2^-40 max(1, g_0 .. g_i) per component and
+ * 2^-40 max(1, g_0 .. g_i) on the gain -- closer to it than the reference's float loop is, and therefore not that loop's bits.
+ * The scan holds for a row and call if the carried gain is finite and >= 0, 0 <= set_point * rate < inf, max_gain >= 0,
+ * rate >= 0, and every sample is finite with rate * |in[i]| <= 1.  This is decided on the device, per row and call, without the
+ * host waiting.  A row that fails is run by the reference's loop in float instead, serially by one wave (slow: INTEGRATION.md),
+ * from (float) of its gain: outputs and gain are then the float loop's bit for bit, NaN, Inf and negative gains included, and a
+ * NaN gain stays NaN until set_gain / reset, as in the reference.  The other rows of the call are not affected.
+ * set: chan -1 = every channel; takes effect from the next call; NaN parameters are QDSP_HIP_EINVAL.  set_gain: chan -1 = every
+ * channel, any value.  set / get_gain / set_gain / reset synchronise the device; reset puts every gain back to 1.
+ * process / process_ex (nchan 1; link codes as for every *_process_ex; `count` <= max_block where a side is on the host, else
+ * QDSP_HIP_ESIZE).  process_dev: the nchan rows back to back (strides = count).  Device pointers: 8-byte aligned; 16-byte
+ * aligned rows with even strides take the vector loads and stores.  In place (d_out == d_in, with out_stride == in_stride) is
+ * supported and gives the same bits, for both kinds of row; any other overlap of input and output is not. */
+int qdsp_hip_cagc_create(void** h, int device, int nchan, int max_block);
+int qdsp_hip_cagc_set(void* h, int chan, float set_point, float max_gain, float rate);
+int qdsp_hip_cagc_get_gain(void* h, int chan, double* gain);
+int qdsp_hip_cagc_set_gain(void* h, int chan, double gain);
+int qdsp_hip_cagc_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_cagc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_cagc_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_cagc_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                    int64_t out_stride, void* hip_stream);
+int qdsp_hip_cagc_reset(void* h);
+void qdsp_hip_cagc_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

@@ -5,6 +5,7 @@
 #include "level.hip.h"
 #include "stereo_fm.hip.h"
 #include "ff_agc.hip.h"
+#include "cagc.hip.h"
 
 namespace qh {
 
@@ -187,6 +188,10 @@ int qdsp_hip_set_done_event(void* h, void* ev) {
         d->done_ev = static_cast<hipEvent_t>(ev);
         return 0;
     }
+    if (Cagc* d = as_cagc(h)) {
+        d->done_ev = static_cast<hipEvent_t>(ev);
+        return 0;
+    }
     Engine* e = any_engine(h);
     if (!e) return QDSP_HIP_EINVAL;
     e->done_ev = static_cast<hipEvent_t>(ev);
@@ -201,6 +206,7 @@ int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* bloc
     else if (Level* d = as_level(h)) l = &d->last;
     else if (StereoFm* d = as_stereo_fm(h)) l = &d->last;
     else if (FfAgc* d = as_ff_agc(h)) l = &d->last;
+    else if (Cagc* d = as_cagc(h)) l = &d->last;
     else if (Engine* e = any_engine(h)) l = &e->last;
     if (!l) return QDSP_HIP_EINVAL;
     if (name && name_len > 0) { strncpy(name, l->name, name_len - 1); name[name_len - 1] = 0; }
@@ -216,6 +222,7 @@ int qdsp_hip_time_process_dev(void* h, const void* d_in, int64_t count, void* d_
     if (Level* d = as_level(h)) return level_time(d, d_in, count, d_out, stream, iters, ms);
     if (StereoFm* d = as_stereo_fm(h)) return stereo_fm_time(d, d_in, count, d_out, stream, iters, ms);
     if (FfAgc* d = as_ff_agc(h)) return ff_agc_time(d, d_in, count, d_out, stream, iters, ms);
+    if (Cagc* d = as_cagc(h)) return cagc_time(d, d_in, count, d_out, stream, iters, ms);
     Engine* e = any_engine(h);
     return e ? time_process(e, d_in, count, d_out, stream, iters, ms) : QDSP_HIP_EINVAL;
 }

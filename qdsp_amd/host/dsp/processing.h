@@ -1,5 +1,5 @@
-// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch, dsp::AGC and dsp::FeedForwardAGC<T>, HIP-backed (the
-// reference's other blocks in this header -- ComplexAGC, packer ... -- are not provided).
+// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch, dsp::AGC, dsp::FeedForwardAGC<T> and dsp::ComplexAGC, HIP-backed
+// (the reference's other blocks in this header -- DelayImag, packer ... -- are not provided).
 //
 // Drop-in for src/dsp/processing.h:10-81.  init()/setSampleRate()/setFrequency() compute
 // phaseDelta exactly as the reference does -- theta = (freq/sampleRate) * 2.0f * FL_M_PI in
@@ -346,6 +346,108 @@ public:
 private:
     int sampleCount = 1024;
     stream<T>* _in = nullptr;
+    void* handle = nullptr;
+    detail::done_events done;
+};
+
+// ComplexAGC (src/dsp/processing.h:235-298): same constructors, init(), setInput(), setSetPoint(), setMaxGain(), setRate() and
+// `out`.  The gain lives on the device in FP64 (qdsp_hip_cagc_*); a setter acts from the next run().  The outputs follow the exact
+// recurrence of the float parameters more closely than the reference's float loop does, so they are not that loop's bits
+// (INTEGRATION.md).
+class ComplexAGC : public generic_block<ComplexAGC> {
+    using base = generic_block<ComplexAGC>;
+
+public:
+    ComplexAGC() {}
+
+    ComplexAGC(stream<complex_t>* in, float setPoint, float maxGain, float rate) { init(in, setPoint, maxGain, rate); }
+
+    ~ComplexAGC() {
+        const bool live = base::running;
+        base::stop();
+        if (live && _in) { _in->releaseConsumer(); }
+        if (handle) { qdsp_hip_cagc_destroy(handle); }
+    }
+
+    void init(stream<complex_t>* in, float setPoint, float maxGain, float rate) {
+        _in = in;
+        _setPoint = setPoint;
+        _maxGain = maxGain;
+        _rate = rate;
+        int rc = qdsp_hip_cagc_create(&handle, detail::hipDeviceForBlocks(), 1, STREAM_BUFFER_SIZE);
+        if (rc == 0) { rc = qdsp_hip_cagc_set(handle, 0, _setPoint, _maxGain, _rate); }
+        if (rc != 0) { handle = nullptr; detail::hipBlockFail("ComplexAGC::init", rc); }
+        base::registerInput(_in);
+        base::registerOutput(&out);
+        _in->claimConsumer(handle != nullptr, true);
+    }
+
+    void setInput(stream<complex_t>* in) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        base::unregisterInput(_in);
+        _in->releaseConsumer();
+        _in = in;
+        _in->claimConsumer(handle != nullptr, true);
+        base::registerInput(_in);
+        base::tempStart();
+    }
+
+    void setSetPoint(float setPoint) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        _setPoint = setPoint;
+        push();
+        base::tempStart();
+    }
+
+    void setMaxGain(float maxGain) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        _maxGain = maxGain;
+        push();
+        base::tempStart();
+    }
+
+    void setRate(float rate) {
+        std::lock_guard<std::mutex> lck(base::ctrlMtx);
+        base::tempStop();
+        _rate = rate;
+        push();
+        base::tempStart();
+    }
+
+    int run() override {
+        const int count = _in->read();
+        if (count < 0) { return -1; }
+        if (!handle) { return -1; }
+        const bool inDev = _in->readOnDevice;
+        const bool outDev = out.consumerTakesDevice && out.ensureDevice(detail::hipDeviceForBlocks());
+        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
+        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
+        void* evt = nullptr;
+        const int outLink = outDev ? out.linkOut(true) : done.arm(handle, evt);
+        const int rc = qdsp_hip_cagc_process_ex(handle, src, _in->linkIn(), count, dst, outLink);
+        _in->flush();
+        if (rc != 0) { return detail::hipBlockFail("ComplexAGC::run", rc); }
+        out.markWritten(outLink, evt);
+        if (!out.swap(count)) { return -1; }
+        return count;
+    }
+
+    stream<complex_t> out;
+
+private:
+    void push() {
+        if (!handle) { return; }
+        const int rc = qdsp_hip_cagc_set(handle, 0, _setPoint, _maxGain, _rate);
+        if (rc != 0) { detail::hipBlockFail("ComplexAGC::set", rc); }
+    }
+
+    float _setPoint = 1.0f;
+    float _maxGain = 10e4;
+    float _rate = 10e-4;
+    stream<complex_t>* _in = nullptr;
     void* handle = nullptr;
     detail::done_events done;
 };

@@ -21,6 +21,8 @@
 //                   source -> VFO -> FeedForwardAGC<complex_t> (dsp/processing.h) -> sink: 1023 samples fewer out than the VFO gives
 //                   (the harness counts one output block per input block and the block publishes nothing while it fills, so a
 //                   <block> whose VFO output is below 1024 samples is refused)
+//   demod_check cagc <dev|host> <in.cf32> <out.cf32> <block> <offset> <inSR> <outSR> <bw> <set_point> <max_gain> <rate>
+//                   source -> VFO -> ComplexAGC (dsp/processing.h) -> sink
 //   demod_check sfm <in.cf32> <out> <block> <sampleRate> <deviation>
 //                   source -> StereoFMDemod (dsp/stereo_demod.h) -> sink: the file is the demodulator's own input, read in blocks of
 //                   <block> samples, one run() each; stereo_t out.
@@ -208,6 +210,11 @@ int main(int argc, char** argv) {
         if ((double)block * outSR / inSR < 1024.0) { fprintf(stderr, "ffagc: <block> * outSR / inSR must be at least 1024\n"); return 2; }
         return runGraph<complex_t>(in, out, block, off, inSR, outSR, bw, hostLink,
                                    [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new FeedForwardAGC<complex_t>(s), b); });
+    }
+    if (mode == "cagc" && argc > 12) {
+        const float maxGain = (float)atof(argv[11]), rate = (float)atof(argv[12]);
+        return runGraph<complex_t>(in, out, block, off, inSR, outSR, bw, hostLink,
+                                   [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new ComplexAGC(s, p1, maxGain, rate), b); });
     }
     fprintf(stderr, "unknown mode %s\n", mode.c_str());
     return 2;

@@ -1057,3 +1057,41 @@ class FeedForwardAgc(_RowOp):
 
 
 __all__ += ["FeedForwardAgc"]
+
+
+class ComplexAgc(_Level):
+    """dsp::ComplexAGC (src/dsp/processing.h:235-298): out[i] = x[i] g; g += (set_point - |out[i]|) rate; g = min(g, max_gain),
+    per sample, run as an FP64 clamped prefix scan (include/qdsp_hip.h: complex AGC).  `nchan` complex64 rows per launch, each
+    with its own parameters (scalars or one value per channel) and gain.  A row the scan does not cover in a call -- a NaN or Inf
+    sample, rate |x| > 1, a negative, NaN or Inf gain, set_point rate < 0 -- is run by the reference's float loop on the device
+    instead, serially.  Entry points by input as for Squelch and Agc; out=x works in place."""
+
+    _prefix = "qdsp_hip_cagc"
+    _np, _tt = np.complex64, "complex64"
+
+    def __init__(self, set_point=1.0, max_gain=1e5, rate=1e-3, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_cagc_create")
+        sps = np.broadcast_to(np.asarray(set_point, dtype=np.float32), (self.nchan,))
+        mgs = np.broadcast_to(np.asarray(max_gain, dtype=np.float32), (self.nchan,))
+        rts = np.broadcast_to(np.asarray(rate, dtype=np.float32), (self.nchan,))
+        for c in range(self.nchan):
+            self.set(float(sps[c]), float(mgs[c]), float(rts[c]), c)
+
+    def set(self, set_point: float, max_gain: float, rate: float, chan: int = -1):
+        """Takes effect from the next call."""
+        capi.check(self._fn("set")(self._h, int(chan), set_point, max_gain, rate), "qdsp_hip_cagc_set")
+
+    def get_gain(self, chan: int = 0) -> float:
+        """The carried gain, FP64 (synchronises the device)."""
+        v = C.c_double()
+        capi.check(self._fn("get_gain")(self._h, int(chan), C.byref(v)))
+        return float(v.value)
+
+    def set_gain(self, gain: float, chan: int = -1):
+        capi.check(self._fn("set_gain")(self._h, int(chan), float(gain)))
+
+
+__all__ += ["ComplexAgc"]
