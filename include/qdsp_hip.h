@@ -549,6 +549,41 @@ int qdsp_hip_cagc_process_batch_dev(void* h, const void* d_in, int64_t count, in
 int qdsp_hip_cagc_reset(void* h);
 void qdsp_hip_cagc_destroy(void* h);
 
+/* ---- Costas loop : CostasLoop<ORDER>, src/dsp/pll.h:47-102 ------------------------------------ */
+/* The carrier-recovery loop of PSKDemod on complex_t rows; nchan channel-major rows per call, strides in samples, one order (2, 4
+ * or 8) per handle, each channel with its own loop bandwidth, frequency and phase (FP64, on the device, both 0 at creation):
+ *   out[i] = vco * in[i];  e = the order's phase error of out[i], clamped to +-1;  freq = clamp(freq + beta e, +-1);
+ *   phase += freq + alpha e, wrapped into [-T, T], T = the reference's float 2 pi;  vco = (cos(-phase), sin(-phase))
+ * A row is serial; the rows are independent and run one per lane, 16 to a wave.  alpha and beta are the reference's floats (its
+ * formula, evaluated on the host); everything else is FP64 and every output is rounded to float once, so the outputs follow the
+ * exact recurrence more closely than the reference's float loop does and are not that loop's bits.  Outputs and state do not
+ * depend, bit for bit, on how a stream is cut into calls, on the row's place in the batch, on strides, alignment, in-place use
+ * or the entry point.
+ * Departures from the reference: (1) set_bandwidth takes a finite bandwidth >= 0 whose alpha and beta are finite, anything else is
+ * QDSP_HIP_EINVAL: then |freq + alpha e| < 2 pi and the phase is wrapped by one conditional step each way where the reference
+ * loops (for ever, on an infinite phase).  (2) A NaN sample makes its row's outputs NaN from that sample to the end of the call,
+ * as in the reference, and leaves the row's state NaN; a carried frequency or phase that is not finite reads as 0 at the next
+ * call, where the reference stays NaN for ever.  Other rows are not affected.
+ * create: the bandwidth is the reference's default 1.0 until set.  set_bandwidth / set_state: chan -1 = every channel; they act
+ * from the next call.  set_state: a finite phase beyond +-T is QDSP_HIP_EINVAL.  set_bandwidth / get_state / set_state / reset
+ * synchronise the device; reset puts every frequency and phase back to 0.  get_gains: the alpha and beta in use.
+ * process / process_ex (nchan 1; link codes as for every *_process_ex; `count` <= max_block where a side is on the host, else
+ * QDSP_HIP_ESIZE).  process_dev: the nchan rows back to back (strides = count).  Device pointers: 8-byte aligned.  In place
+ * (d_out == d_in, with out_stride == in_stride) is supported and gives the same bits; any other overlap is not.  count 0 launches
+ * nothing and keeps the state. */
+int qdsp_hip_costas_create(void** h, int device, int order, int nchan, int max_block);
+int qdsp_hip_costas_set_bandwidth(void* h, int chan, float bandwidth);
+int qdsp_hip_costas_get_gains(void* h, int chan, float* alpha, float* beta);
+int qdsp_hip_costas_get_state(void* h, int chan, double* freq, double* phase);
+int qdsp_hip_costas_set_state(void* h, int chan, double freq, double phase);
+int qdsp_hip_costas_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_costas_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_costas_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_costas_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                      int64_t out_stride, void* hip_stream);
+int qdsp_hip_costas_reset(void* h);
+void qdsp_hip_costas_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

@@ -249,6 +249,18 @@ def load():
     sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp)
     sig(p + "_reset", i32, vp)
     sig(p + "_destroy", None, vp)
+    p = "qdsp_hip_costas"
+    sig(p + "_create", i32, pvp, i32, i32, i32, i32)
+    sig(p + "_set_bandwidth", i32, vp, i32, C.c_float)
+    sig(p + "_get_gains", i32, vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float))
+    sig(p + "_get_state", i32, vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double))
+    sig(p + "_set_state", i32, vp, i32, C.c_double, C.c_double)
+    sig(p + "_process", i32, vp, vp, i32, vp)
+    sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+    sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp)
+    sig(p + "_reset", i32, vp)
+    sig(p + "_destroy", None, vp)
     sig("qdsp_hip_set_done_event", i32, vp, vp)
     sig("qdsp_hip_event_create", i32, i32, pvp)
     sig("qdsp_hip_event_destroy", i32, vp)

@@ -6,6 +6,7 @@
 #include "stereo_fm.hip.h"
 #include "ff_agc.hip.h"
 #include "cagc.hip.h"
+#include "costas.hip.h"
 
 namespace qh {
 
@@ -192,6 +193,10 @@ int qdsp_hip_set_done_event(void* h, void* ev) {
         d->done_ev = static_cast<hipEvent_t>(ev);
         return 0;
     }
+    if (Costas* d = as_costas(h)) {
+        d->done_ev = static_cast<hipEvent_t>(ev);
+        return 0;
+    }
     Engine* e = any_engine(h);
     if (!e) return QDSP_HIP_EINVAL;
     e->done_ev = static_cast<hipEvent_t>(ev);
@@ -207,6 +212,7 @@ int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* bloc
     else if (StereoFm* d = as_stereo_fm(h)) l = &d->last;
     else if (FfAgc* d = as_ff_agc(h)) l = &d->last;
     else if (Cagc* d = as_cagc(h)) l = &d->last;
+    else if (Costas* d = as_costas(h)) l = &d->last;
     else if (Engine* e = any_engine(h)) l = &e->last;
     if (!l) return QDSP_HIP_EINVAL;
     if (name && name_len > 0) { strncpy(name, l->name, name_len - 1); name[name_len - 1] = 0; }
@@ -223,6 +229,7 @@ int qdsp_hip_time_process_dev(void* h, const void* d_in, int64_t count, void* d_
     if (StereoFm* d = as_stereo_fm(h)) return stereo_fm_time(d, d_in, count, d_out, stream, iters, ms);
     if (FfAgc* d = as_ff_agc(h)) return ff_agc_time(d, d_in, count, d_out, stream, iters, ms);
     if (Cagc* d = as_cagc(h)) return cagc_time(d, d_in, count, d_out, stream, iters, ms);
+    if (Costas* d = as_costas(h)) return costas_time(d, d_in, count, d_out, stream, iters, ms);
     Engine* e = any_engine(h);
     return e ? time_process(e, d_in, count, d_out, stream, iters, ms) : QDSP_HIP_EINVAL;
 }

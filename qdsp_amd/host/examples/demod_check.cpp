@@ -23,6 +23,8 @@
 //                   <block> whose VFO output is below 1024 samples is refused)
 //   demod_check cagc <dev|host> <in.cf32> <out.cf32> <block> <offset> <inSR> <outSR> <bw> <set_point> <max_gain> <rate>
 //                   source -> VFO -> ComplexAGC (dsp/processing.h) -> sink
+//   demod_check costas <dev|host> <in.cf32> <out.cf32> <block> <offset> <inSR> <outSR> <bw> <order> <loop_bandwidth>
+//                   source -> VFO -> CostasLoop<order> (dsp/pll.h), order 2, 4 or 8 -> sink
 //   demod_check sfm <in.cf32> <out> <block> <sampleRate> <deviation>
 //                   source -> StereoFMDemod (dsp/stereo_demod.h) -> sink: the file is the demodulator's own input, read in blocks of
 //                   <block> samples, one run() each; stereo_t out.
@@ -38,6 +40,7 @@
 
 #include <dsp/deemp.h>
 #include <dsp/demodulator.h>
+#include <dsp/pll.h>
 #include <dsp/processing.h>
 #include <dsp/sink.h>
 #include <dsp/source.h>
@@ -215,6 +218,19 @@ int main(int argc, char** argv) {
         const float maxGain = (float)atof(argv[11]), rate = (float)atof(argv[12]);
         return runGraph<complex_t>(in, out, block, off, inSR, outSR, bw, hostLink,
                                    [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { return with(new ComplexAGC(s, p1, maxGain, rate), b); });
+    }
+    if (mode == "costas" && argc > 11) {
+        const int order = (int)p1;
+        const float loopBw = (float)atof(argv[11]);
+        auto make = [&](auto* d) {
+            return runGraph<complex_t>(in, out, block, off, inSR, outSR, bw, hostLink,
+                                       [&](stream<complex_t>* s, std::vector<generic_unnamed_block*>& b) { d->init(s, loopBw); return with(d, b); });
+        };
+        if (order == 2) { return make(new CostasLoop<2>()); }
+        if (order == 4) { return make(new CostasLoop<4>()); }
+        if (order == 8) { return make(new CostasLoop<8>()); }
+        fprintf(stderr, "costas: order 2, 4 or 8\n");
+        return 2;
     }
     fprintf(stderr, "unknown mode %s\n", mode.c_str());
     return 2;

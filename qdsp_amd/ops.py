@@ -1095,3 +1095,48 @@ class ComplexAgc(_Level):
 
 
 __all__ += ["ComplexAgc"]
+
+
+class CostasLoop(_Level):
+    """dsp::CostasLoop<ORDER> (src/dsp/pll.h:47-102), ORDER 2, 4 or 8: out = vco x; the order's phase error of out, clamped, moves
+    the frequency (beta) and the phase (alpha); vco = exp(-j phase).  One row per lane, 16 rows to a wave (include/qdsp_hip.h: Costas
+    loop).  `nchan` complex64 rows per launch, each with its own loop bandwidth (a scalar or one value per channel), frequency and
+    phase (FP64, on the device).  Entry points by input as for Squelch and Agc; out=x works in place."""
+
+    _prefix = "qdsp_hip_costas"
+    _np, _tt = np.complex64, "complex64"
+
+    def __init__(self, order: int, bandwidth, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.order = int(order)
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.order, self.nchan, max_block), "qdsp_hip_costas_create")
+        bws = np.broadcast_to(np.asarray(bandwidth, dtype=np.float32), (self.nchan,))
+        if np.all(bws == bws[0]):
+            self.set_bandwidth(float(bws[0]))
+        else:
+            for c in range(self.nchan):
+                self.set_bandwidth(float(bws[c]), c)
+
+    def set_bandwidth(self, bandwidth: float, chan: int = -1):
+        """Takes effect from the next call; finite and >= 0."""
+        capi.check(self._fn("set_bandwidth")(self._h, int(chan), bandwidth), "qdsp_hip_costas_set_bandwidth")
+
+    def gains(self, chan: int = 0):
+        """(alpha, beta) in use, the reference's floats."""
+        a, b = C.c_float(), C.c_float()
+        capi.check(self._fn("get_gains")(self._h, int(chan), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
+    def get_state(self, chan: int = 0):
+        """The carried (frequency, phase), FP64 (synchronises the device)."""
+        f, p = C.c_double(), C.c_double()
+        capi.check(self._fn("get_state")(self._h, int(chan), C.byref(f), C.byref(p)))
+        return float(f.value), float(p.value)
+
+    def set_state(self, freq: float, phase: float, chan: int = -1):
+        capi.check(self._fn("set_state")(self._h, int(chan), float(freq), float(phase)), "qdsp_hip_costas_set_state")
+
+
+__all__ += ["CostasLoop"]
