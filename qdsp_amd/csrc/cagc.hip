@@ -1,6 +1,7 @@
 // cagc.hip -- ComplexAGC as a batched FP64 clamped prefix scan, its serial path for rows out of the scan's domain (design notes:
 // cagc.hip.h) and its C entry points.
 #include "cagc.hip.h"
+#include "scan.hip.h"
 
 #include <cfloat>
 
@@ -10,9 +11,8 @@ namespace {
 // g -> min(a g + b, c)
 struct Clamp {
     double a, b, c;
+    static __device__ __forceinline__ Clamp identity() { return Clamp{1.0, 0.0, DBL_MAX}; }
 };
-
-__device__ __forceinline__ Clamp clamp_identity() { return Clamp{1.0, 0.0, DBL_MAX}; }
 
 // `later` after `earlier`
 __device__ __forceinline__ Clamp compose(const Clamp& later, const Clamp& earlier) {
@@ -59,7 +59,7 @@ __device__ __forceinline__ void lane_coeffs(const float (&x)[kDemodSpl * 2], int
 
 // the lane's n samples as one map
 __device__ __forceinline__ Clamp fold_lane(const double (&aj)[kDemodSpl], int n, double b, double c) {
-    Clamp p = clamp_identity();
+    Clamp p = Clamp::identity();
 #pragma unroll
     for (int j = 0; j < kDemodSpl; j++) {
         if (j < n) {
@@ -69,37 +69,6 @@ __device__ __forceinline__ Clamp fold_lane(const double (&aj)[kDemodSpl], int n,
         }
     }
     return p;
-}
-
-// One tile: from every lane's own map, the map of all lanes before it (*ex) and of the whole tile (returned); the tree of
-// deemp.hip's tile_scan.
-__device__ __forceinline__ Clamp tile_scan(const Clamp& p, Clamp* wt, Clamp* ex) {
-    constexpr int NW = kDemodNT / 64;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    Clamp inc = p;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const Clamp q = shfl_up(inc, d);
-        if (lane >= d) inc = compose(inc, q);
-    }
-    if (lane == 63) wt[w] = inc;
-    __syncthreads();
-    Clamp e = shfl_up(inc, 1);
-    if (lane == 0) e = clamp_identity();
-    Clamp pre = clamp_identity(), tot = clamp_identity();
-#pragma unroll
-    for (int k = 0; k < NW; k++) {
-        const Clamp t = wt[k];
-        if (k < w) pre = compose(t, pre);
-        tot = compose(t, tot);
-    }
-    *ex = compose(e, pre);
-    __syncthreads();   // (wt is written again by the next tile)
-    return tot;
-}
-
-__device__ __forceinline__ long long tiles_of(long long count) {
-    return (count + (long long)kDemodNT * kDemodSpl - 1) / ((long long)kDemodNT * kDemodSpl);
 }
 
 // whether pass 1 found the row out of the domain: the flags of all G chunks (every lane of the workgroup gets the answer)
@@ -117,7 +86,7 @@ __device__ __forceinline__ void scan_chunk(const CagcArgs& a, const RowPar& p, C
     for (int k = 0; k < g; k++) carry = fmin(fma(part[k * kCagcPart], carry, part[k * kCagcPart + 1]), part[k * kCagcPart + 2]);
     const float* in = a.in + (long long)ch * a.in_stride * 2;
     float* out = a.out + (long long)ch * a.out_stride * 2;
-    const long long tiles = tiles_of(a.count);
+    const long long tiles = scan_tiles_of(a.count);
     const long long t0 = (long long)g * a.T;
     const long long t1 = t0 + a.T < tiles ? t0 + a.T : tiles;
     for (long long t = t0; t < t1; t++) {
@@ -152,7 +121,7 @@ __global__ __launch_bounds__(kDemodNT) void cagc_row_kernel(const CagcArgs a) {
     const RowPar p = row_par(a, ch);
     const float* in = a.in + (long long)ch * a.in_stride * 2;
     bool bad = !p.ok;
-    const long long tiles = tiles_of(a.count);
+    const long long tiles = scan_tiles_of(a.count);
     for (long long t = 0; t < tiles; t++) {
         const long long i0 = (t * kDemodNT + threadIdx.x) * kDemodSpl;
         float x[kDemodSpl * 2];
@@ -172,9 +141,9 @@ __global__ __launch_bounds__(kDemodNT) void cagc_partial_kernel(const CagcArgs a
     const int ch = blockIdx.y, g = blockIdx.x;
     const RowPar p = row_par(a, ch);
     const float* in = a.in + (long long)ch * a.in_stride * 2;
-    Clamp acc = clamp_identity();
+    Clamp acc = Clamp::identity();
     bool bad = !p.ok;
-    const long long tiles = tiles_of(a.count);
+    const long long tiles = scan_tiles_of(a.count);
     const long long t0 = (long long)g * a.T;
     const long long t1 = t0 + a.T < tiles ? t0 + a.T : tiles;
     for (long long t = t0; t < t1; t++) {
@@ -238,28 +207,24 @@ __global__ __launch_bounds__(64) void cagc_serial_kernel(const CagcArgs a) {
 namespace qh {
 
 namespace {
-bool chan_ok(const Cagc* d, int chan) { return chan >= 0 && chan < d->nchan; }
 
 void cagc_free(Cagc* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {d->d_in, d->d_out, (void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par, (void*)d->d_part})
+    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par, (void*)d->d_part})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
 int cagc_fill_state(Cagc* d, int chan, double gain, bool both) {
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
-    const int c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
-    const std::vector<double> v((size_t)n, gain);
+    const std::vector<double> v((size_t)chan_count(d, chan), gain);
     for (int s = 0; s < 2; s++)
-        if (both || s == d->cur) HIPCHK(hipMemcpy(d->d_state[s] + c0, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (both || s == d->cur)
+            HIPCHK(hipMemcpy(d->d_state[s] + chan_first(chan), v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -271,8 +236,7 @@ int cagc_launch(Cagc* d, const void* d_in, int64_t count, int64_t in_stride, voi
     if (d_in == d_out && in_stride != out_stride) return QDSP_HIP_EINVAL;   // in place: the same rows exactly
     if (count == 0) return 0;
     HIPCHK(hipSetDevice(d->device));
-    const long long per_wg = (long long)qk::kDemodNT * qk::kDemodSpl;
-    const long long tiles = (count + per_wg - 1) / per_wg;
+    const long long tiles = qk::scan_tiles_of(count);
     qk::CagcArgs a;
     a.in = static_cast<const float*>(d_in);
     a.out = static_cast<float*>(d_out);
@@ -285,16 +249,12 @@ int cagc_launch(Cagc* d, const void* d_in, int64_t count, int64_t in_stride, voi
     a.out_stride = out_stride;
     a.vec = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0 && in_stride % 2 == 0 && out_stride % 2 == 0;
     const int lds = (int)((qk::kDemodNT / 64) * 3 * sizeof(double));
-    if (tiles <= qk::kCagcRowTiles) {
-        a.T = tiles;
-        a.G = 1;
+    qk::scan_chunks(tiles, qk::kCagcRowTiles, &a.T, &a.G);
+    if (a.G == 1) {
         hipLaunchKernelGGL(qk::cagc_row_kernel, dim3(1, (unsigned)d->nchan), dim3(qk::kDemodNT), 0, s, a);
         HIPCHK(hipGetLastError());
         d->last = Launch{"cagc_row_kernel", 1, qk::kDemodNT, lds};
     } else {
-        const long long g0 = tiles < qk::kAmMaxParts ? tiles : qk::kAmMaxParts;
-        a.T = (tiles + g0 - 1) / g0;
-        a.G = (int)((tiles + a.T - 1) / a.T);
         const dim3 grid((unsigned)a.G, (unsigned)d->nchan);
         hipLaunchKernelGGL(qk::cagc_partial_kernel, grid, dim3(qk::kDemodNT), 0, s, a);
         HIPCHK(hipGetLastError());
@@ -308,62 +268,7 @@ int cagc_launch(Cagc* d, const void* d_in, int64_t count, int64_t in_stride, voi
     return 0;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
-int cagc_process_ex(Cagc* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const size_t bytes = (size_t)count * 2 * sizeof(float);
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    int rc = cagc_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
-    if (rc) return rc;
-    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, bytes, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return 0;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return 0;
-}
 }  // namespace
-
-int cagc_time(Cagc* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int rc = cagc_launch(d, d_in, count, count, d_out, count, s);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
-}
 
 }  // namespace qh
 
@@ -372,30 +277,18 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_cagc_create(void** h, int device, int nchan, int max_block) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
-    if (nchan < 1 || nchan > kDemodMaxChan || max_block < 0) return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (h) *h = nullptr;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     Cagc* d = new (std::nothrow) Cagc();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
-    d->nchan = nchan;
-    d->max_block = max_block;
+    d->launch = launch_as<Cagc, cagc_launch>;
     d->par.resize((size_t)nchan * 3);
     for (int c = 0; c < nchan; c++) {   // the reference's defaults (processing.h:291-294)
         d->par[3 * c] = 1.0f;
         d->par[3 * c + 1] = 10e4f;
         d->par[3 * c + 2] = 10e-4f;
     }
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    const size_t io_b = (size_t)max_block * 2 * sizeof(float);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, io_b);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, io_b);
+    hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float2), sizeof(float2));
     const std::vector<double> ones((size_t)nchan, 1.0);
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_state[i], (size_t)nchan * sizeof(double));
@@ -415,24 +308,17 @@ int qdsp_hip_cagc_set(void* h, int chan, float set_point, float max_gain, float 
     Cagc* d = as_cagc(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (std::isnan(set_point) || std::isnan(max_gain) || std::isnan(rate)) return QDSP_HIP_EINVAL;
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) {
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
         d->par[3 * c] = set_point;
         d->par[3 * c + 1] = max_gain;
         d->par[3 * c + 2] = rate;
     }
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
-    HIPCHK(hipMemcpy(d->d_par, d->par.data(), d->par.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return sync_upload(d, d->d_par, d->par.data(), d->par.size() * sizeof(float));
 }
 int qdsp_hip_cagc_get_gain(void* h, int chan, double* gain) {
     Cagc* d = as_cagc(h);
     if (!d || !chan_ok(d, chan) || !gain) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(gain, d->d_state[d->cur] + chan, sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return sync_download(d, gain, d->d_state[d->cur] + chan, sizeof(double));
 }
 int qdsp_hip_cagc_set_gain(void* h, int chan, double gain) {
     Cagc* d = as_cagc(h);
@@ -441,7 +327,7 @@ int qdsp_hip_cagc_set_gain(void* h, int chan, double gain) {
 }
 int qdsp_hip_cagc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Cagc* d = as_cagc(h);
-    return d ? cagc_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_cagc_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_cagc_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);

@@ -10,7 +10,8 @@
 //   cannot repeat the reference's float loop bit for bit; it is held to the exact recurrence instead (tests/test_gpu_cagc.py).
 //   The identity that pads ragged tiles and stands left of lane 0 is (1, 0, DBL_MAX), not (1, 0, +inf): a sample with a == 0
 //   exactly (rate |x| == 1) would meet it as 0 * inf.  A maxGain of +inf is clamped to DBL_MAX for the same reason.
-//   Tile = kDemodNT lanes x kDemodSpl consecutive samples, scanned as in deemp.hip.h.
+//   Tile = kDemodNT lanes x kDemodSpl consecutive samples, scanned as in deemp.hip.h: the same tile_scan and chunk geometry
+//   (scan.hip.h), here over Clamp maps.
 //     cagc_row_kernel      short rows, one launch: one workgroup per channel sweeps the row once to check the domain, then tile by tile
 //     cagc_partial_kernel  long rows, pass 1: workgroup g folds the T tiles of chunk g into one FP64 triple and records whether
 //                          every sample of the chunk is in the domain
@@ -56,29 +57,17 @@ struct CagcArgs {
 
 namespace qh {
 
-constexpr uint32_t kCagcMagic = 0x51434147u;  // "QCAG"
-struct Cagc {
-    uint32_t magic = kCagcMagic;
-    int device = 0;
-    int nchan = 1;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
+struct Cagc : StreamOp {
+    Cagc() : StreamOp(kCagcMagic) {}
     double* d_state[2] = {nullptr, nullptr};
     int cur = 0;
     float* d_par = nullptr;
     std::vector<float> par;                // [nchan][3]
     double* d_part = nullptr;
-    Launch last;
 };
 inline Cagc* as_cagc(void* h) {
     Cagc* d = static_cast<Cagc*>(h);
     return (d && d->magic == kCagcMagic) ? d : nullptr;
 }
-int cagc_time(Cagc* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 
 }  // namespace qh

@@ -184,7 +184,6 @@ template <int ORDER> __global__ __launch_bounds__(kCostasLanes) void costas_kern
 namespace qh {
 
 namespace {
-bool chan_ok(const Costas* d, int chan) { return chan >= 0 && chan < d->nchan; }
 
 // pll.h:20-23: the damping factor and the coefficients are floats, the denominator is summed in double and rounded to float
 bool costas_gains(float bw, float* alpha, float* beta) {
@@ -201,19 +200,16 @@ void costas_free(Costas* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {d->d_in, d->d_out, (void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par})
+    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
 int costas_fill_state(Costas* d, int chan, double freq, double phase, bool both) {
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
-    const int c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
+    const int c0 = chan_first(chan), n = chan_count(d, chan);
     std::vector<double> v((size_t)n * 2);
     for (int c = 0; c < n; c++) {
         v[2 * c] = freq;
@@ -252,62 +248,7 @@ int costas_launch(Costas* d, const void* d_in, int64_t count, int64_t in_stride,
     return 0;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
-int costas_process_ex(Costas* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const size_t bytes = (size_t)count * 2 * sizeof(float);
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    int rc = costas_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
-    if (rc) return rc;
-    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, bytes, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return 0;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return 0;
-}
 }  // namespace
-
-int costas_time(Costas* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int rc = costas_launch(d, d_in, count, count, d_out, count, s);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
-}
 
 }  // namespace qh
 
@@ -316,27 +257,16 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_costas_create(void** h, int device, int order, int nchan, int max_block) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
-    if ((order != 2 && order != 4 && order != 8) || nchan < 1 || nchan > kDemodMaxChan || max_block < 0) return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (h) *h = nullptr;
+    if (order != 2 && order != 4 && order != 8) return QDSP_HIP_EINVAL;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     Costas* d = new (std::nothrow) Costas();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
     d->order = order;
-    d->nchan = nchan;
-    d->max_block = max_block;
+    d->launch = launch_as<Costas, costas_launch>;
     d->par.resize((size_t)nchan * 2);
     for (int c = 0; c < nchan; c++) (void)costas_gains(1.0f, &d->par[2 * c], &d->par[2 * c + 1]);   // _loopBandwidth = 1.0f (pll.h:107)
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    const size_t io_b = (size_t)max_block * 2 * sizeof(float);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, io_b);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, io_b);
+    hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float2), sizeof(float2));
     const size_t st_b = (size_t)nchan * 2 * sizeof(double);
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_state[i], st_b);
@@ -357,15 +287,11 @@ int qdsp_hip_costas_set_bandwidth(void* h, int chan, float bw) {
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     float alpha = 0.0f, beta = 0.0f;
     if (!costas_gains(bw, &alpha, &beta)) return QDSP_HIP_EINVAL;
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) {
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
         d->par[2 * c] = alpha;
         d->par[2 * c + 1] = beta;
     }
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
-    HIPCHK(hipMemcpy(d->d_par, d->par.data(), d->par.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return sync_upload(d, d->d_par, d->par.data(), d->par.size() * sizeof(float));
 }
 int qdsp_hip_costas_get_gains(void* h, int chan, float* alpha, float* beta) {
     Costas* d = as_costas(h);
@@ -377,10 +303,8 @@ int qdsp_hip_costas_get_gains(void* h, int chan, float* alpha, float* beta) {
 int qdsp_hip_costas_get_state(void* h, int chan, double* freq, double* phase) {
     Costas* d = as_costas(h);
     if (!d || !chan_ok(d, chan) || !freq || !phase) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
     double v[2];
-    HIPCHK(hipMemcpy(v, d->d_state[d->cur] + 2 * chan, sizeof(v), hipMemcpyDeviceToHost));
+    if (const int rc = sync_download(d, v, d->d_state[d->cur] + 2 * chan, sizeof(v))) return rc;
     *freq = v[0];
     *phase = v[1];
     return 0;
@@ -393,7 +317,7 @@ int qdsp_hip_costas_set_state(void* h, int chan, double freq, double phase) {
 }
 int qdsp_hip_costas_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Costas* d = as_costas(h);
-    return d ? costas_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_costas_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_costas_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);

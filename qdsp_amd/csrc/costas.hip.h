@@ -50,29 +50,17 @@ struct CostasArgs {
 
 namespace qh {
 
-constexpr uint32_t kCostasMagic = 0x51434f53u;  // "QCOS"
-struct Costas {
-    uint32_t magic = kCostasMagic;
-    int device = 0;
+struct Costas : StreamOp {
+    Costas() : StreamOp(kCostasMagic) {}
     int order = 2;
-    int nchan = 1;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
     double* d_state[2] = {nullptr, nullptr};
     int cur = 0;
     float* d_par = nullptr;
     std::vector<float> par;                // [nchan][2]
-    Launch last;
 };
 inline Costas* as_costas(void* h) {
     Costas* d = static_cast<Costas*>(h);
     return (d && d->magic == kCostasMagic) ? d : nullptr;
 }
-int costas_time(Costas* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 
 }  // namespace qh

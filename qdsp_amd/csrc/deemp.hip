@@ -1,5 +1,6 @@
 // deemp.hip -- BFMDeemp as a batched FP64 prefix scan (design notes: deemp.hip.h) and its C entry points.
 #include "deemp.hip.h"
+#include "scan.hip.h"
 
 namespace qk {
 
@@ -8,15 +9,14 @@ namespace {
 template <int NC> struct Aff {
     double A;
     double B[NC];
-};
-
-template <int NC> __device__ __forceinline__ Aff<NC> aff_identity() {
-    Aff<NC> r;
-    r.A = 1.0;
+    static __device__ __forceinline__ Aff identity() {
+        Aff r;
+        r.A = 1.0;
 #pragma unroll
-    for (int c = 0; c < NC; c++) r.B[c] = 0.0;
-    return r;
-}
+        for (int c = 0; c < NC; c++) r.B[c] = 0.0;
+        return r;
+    }
+};
 
 // `later` after `earlier`
 template <int NC> __device__ __forceinline__ Aff<NC> compose(const Aff<NC>& later, const Aff<NC>& earlier) {
@@ -37,7 +37,7 @@ template <int NC> __device__ __forceinline__ Aff<NC> shfl_up(const Aff<NC>& v, i
 
 // the lane's n samples as one map
 template <int NC> __device__ __forceinline__ Aff<NC> fold_lane(const float (&x)[kDemodSpl * NC], int n, double a, double b) {
-    Aff<NC> p = aff_identity<NC>();
+    Aff<NC> p = Aff<NC>::identity();
 #pragma unroll
     for (int j = 0; j < kDemodSpl; j++) {
         if (j < n) {
@@ -47,33 +47,6 @@ template <int NC> __device__ __forceinline__ Aff<NC> fold_lane(const float (&x)[
         }
     }
     return p;
-}
-
-// One tile: from every lane's own map, the map of all lanes before it (*ex) and of the whole tile (returned).  Hillis-Steele
-// over the 64 lanes of a wave by cross-lane moves, then the kDemodNT / 64 wave totals through `wt`; always the same tree.
-template <int NC> __device__ __forceinline__ Aff<NC> tile_scan(const Aff<NC>& p, Aff<NC>* wt, Aff<NC>* ex) {
-    constexpr int NW = kDemodNT / 64;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    Aff<NC> inc = p;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const Aff<NC> q = shfl_up(inc, d);
-        if (lane >= d) inc = compose(inc, q);
-    }
-    if (lane == 63) wt[w] = inc;
-    __syncthreads();
-    Aff<NC> e = shfl_up(inc, 1);
-    if (lane == 0) e = aff_identity<NC>();
-    Aff<NC> pre = aff_identity<NC>(), tot = aff_identity<NC>();
-#pragma unroll
-    for (int k = 0; k < NW; k++) {
-        const Aff<NC> t = wt[k];
-        if (k < w) pre = compose(t, pre);
-        tot = compose(t, tot);
-    }
-    *ex = compose(e, pre);
-    __syncthreads();   // (wt is written again by the next tile)
-    return tot;
 }
 
 // chunk g of row c: the carried state moved over the chunks before it, then tile by tile
@@ -95,7 +68,7 @@ template <int NC> __device__ __forceinline__ void scan_chunk(const DeempArgs& a)
     }
     const float* in = a.in + (long long)c * a.in_stride * NC;
     float* out = a.out + (long long)c * a.out_stride * NC;
-    const long long tiles = (a.count + (long long)kDemodNT * kDemodSpl - 1) / ((long long)kDemodNT * kDemodSpl);
+    const long long tiles = scan_tiles_of(a.count);
     const long long t0 = (long long)g * a.T;
     const long long t1 = t0 + a.T < tiles ? t0 + a.T : tiles;
     for (long long t = t0; t < t1; t++) {
@@ -137,7 +110,7 @@ template <int NC> __global__ __launch_bounds__(kDemodNT) void deemp_partial_kern
     const float alpha = a.alpha[c];
     const double al = (double)alpha, b = (double)(1.0f - alpha);
     const float* in = a.in + (long long)c * a.in_stride * NC;
-    Aff<NC> acc = aff_identity<NC>();
+    Aff<NC> acc = Aff<NC>::identity();
     const long long t0 = (long long)g * a.T;
     for (long long t = t0; t < t0 + a.T; t++) {
         const long long i0 = (t * kDemodNT + threadIdx.x) * kDemodSpl;
@@ -160,18 +133,14 @@ namespace qh {
 
 namespace {
 int comps(const Deemp* d) { return d->kind == QDSP_HIP_DEEMP_STEREO ? 2 : 1; }
-bool chan_ok(const Deemp* d, int chan) { return chan >= 0 && chan < d->nchan; }
 
 void deemp_free(Deemp* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {d->d_in, d->d_out, (void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_alpha, (void*)d->d_part})
+    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_alpha, (void*)d->d_part})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
@@ -193,8 +162,7 @@ int deemp_launch(Deemp* d, const void* d_in, int64_t count, int64_t in_stride, v
         d->last = Launch{"bypass", 0, 0, 0};
         return 0;
     }
-    const long long per_wg = (long long)qk::kDemodNT * qk::kDemodSpl;
-    const long long tiles = (count + per_wg - 1) / per_wg;
+    const long long tiles = qk::scan_tiles_of(count);
     qk::DeempArgs a;
     a.in = static_cast<const float*>(d_in);
     a.out = static_cast<float*>(d_out);
@@ -208,18 +176,14 @@ int deemp_launch(Deemp* d, const void* d_in, int64_t count, int64_t in_stride, v
     const int per16 = 4 / nc;   // samples per 16 bytes
     a.vec = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0 && in_stride % per16 == 0 && out_stride % per16 == 0;
     const int lds = (int)((qk::kDemodNT / 64) * (1 + nc) * sizeof(double));
-    if (tiles <= qk::kDeempRowTiles) {
-        a.T = tiles;
-        a.G = 1;
+    qk::scan_chunks(tiles, qk::kDeempRowTiles, &a.T, &a.G);
+    if (a.G == 1) {
         const dim3 grid(1, (unsigned)d->nchan);
         if (nc == 2) hipLaunchKernelGGL((qk::deemp_row_kernel<2>), grid, dim3(qk::kDemodNT), 0, s, a);
         else hipLaunchKernelGGL((qk::deemp_row_kernel<1>), grid, dim3(qk::kDemodNT), 0, s, a);
         HIPCHK(hipGetLastError());
         d->last = Launch{"deemp_row_kernel", 1, qk::kDemodNT, lds};
     } else {
-        const long long g0 = tiles < qk::kAmMaxParts ? tiles : qk::kAmMaxParts;
-        a.T = (tiles + g0 - 1) / g0;
-        a.G = (int)((tiles + a.T - 1) / a.T);   // >= 2: tiles > kDeempRowTiles
         const dim3 g1((unsigned)(a.G - 1), (unsigned)d->nchan), g2((unsigned)a.G, (unsigned)d->nchan);
         if (nc == 2) {
             hipLaunchKernelGGL((qk::deemp_partial_kernel<2>), g1, dim3(qk::kDemodNT), 0, s, a);
@@ -237,62 +201,7 @@ int deemp_launch(Deemp* d, const void* d_in, int64_t count, int64_t in_stride, v
     return 0;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
-int deemp_process_ex(Deemp* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const size_t bytes = (size_t)count * comps(d) * sizeof(float);
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    int rc = deemp_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
-    if (rc) return rc;
-    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, bytes, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return 0;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return 0;
-}
 }  // namespace
-
-int deemp_time(Deemp* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int rc = deemp_launch(d, d_in, count, count, d_out, count, s);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
-}
 
 }  // namespace qh
 
@@ -301,28 +210,16 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_deemp_create(void** h, int device, int kind, int nchan, int max_block) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
-    if ((kind != QDSP_HIP_DEEMP_MONO && kind != QDSP_HIP_DEEMP_STEREO) || nchan < 1 || nchan > kDemodMaxChan || max_block < 0)
-        return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (h) *h = nullptr;
+    if (kind != QDSP_HIP_DEEMP_MONO && kind != QDSP_HIP_DEEMP_STEREO) return QDSP_HIP_EINVAL;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     Deemp* d = new (std::nothrow) Deemp();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
     d->kind = kind;
-    d->nchan = nchan;
-    d->max_block = max_block;
+    d->launch = launch_as<Deemp, deemp_launch>;
     d->alpha.assign(nchan, 1.0f);   // sample_rate 1, tau 0 until set: y = x
     const int nc = comps(d);
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    const size_t io_b = (size_t)max_block * nc * sizeof(float);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, io_b);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, io_b);
+    hipError_t err = stream_op_init(d, device, nchan, max_block, nc * sizeof(float), nc * sizeof(float));
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_state[i], (size_t)nchan * nc * sizeof(double));
         if (err == hipSuccess) err = hipMemset(d->d_state[i], 0, (size_t)nchan * nc * sizeof(double));
@@ -345,12 +242,8 @@ int qdsp_hip_deemp_set(void* h, int chan, float sample_rate, float tau) {
     const float dt = 1.0f / sample_rate;
     const float alpha = dt / (tau + dt);
     if (!std::isfinite(alpha) || alpha <= 0.0f) return QDSP_HIP_EINVAL;
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) d->alpha[c] = alpha;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
-    HIPCHK(hipMemcpy(d->d_alpha, d->alpha.data(), (size_t)d->nchan * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) d->alpha[c] = alpha;
+    return sync_upload(d, d->d_alpha, d->alpha.data(), (size_t)d->nchan * sizeof(float));
 }
 int qdsp_hip_deemp_set_bypass(void* h, int on) {
     Deemp* d = as_deemp(h);
@@ -360,7 +253,7 @@ int qdsp_hip_deemp_set_bypass(void* h, int on) {
 }
 int qdsp_hip_deemp_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Deemp* d = as_deemp(h);
-    return d ? deemp_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deemp_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_deemp_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
@@ -377,11 +270,9 @@ int qdsp_hip_deemp_process_batch_dev(void* h, const void* d_in, int64_t count, i
 int qdsp_hip_deemp_get_state(void* h, int chan, float* l, float* r) {
     Deemp* d = as_deemp(h);
     if (!d || !chan_ok(d, chan) || !l || (comps(d) == 2 && !r)) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
     double v[2] = {0.0, 0.0};
     const int nc = comps(d);
-    HIPCHK(hipMemcpy(v, d->d_state[d->cur] + (size_t)chan * nc, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (const int rc = sync_download(d, v, d->d_state[d->cur] + (size_t)chan * nc, (size_t)nc * sizeof(double))) return rc;
     *l = (float)v[0];
     if (r) *r = (float)v[nc - 1];
     return 0;
@@ -389,16 +280,13 @@ int qdsp_hip_deemp_get_state(void* h, int chan, float* l, float* r) {
 int qdsp_hip_deemp_set_state(void* h, int chan, float l, float r) {
     Deemp* d = as_deemp(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    const int nc = comps(d), c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
+    const int nc = comps(d), n = chan_count(d, chan);
     std::vector<double> v((size_t)n * nc);
     for (int i = 0; i < n; i++) {
         v[(size_t)i * nc] = (double)l;
         if (nc == 2) v[(size_t)i * nc + 1] = (double)r;
     }
-    HIPCHK(hipMemcpy(d->d_state[d->cur] + (size_t)c0 * nc, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
-    return 0;
+    return sync_upload(d, d->d_state[d->cur] + (size_t)chan_first(chan) * nc, v.data(), v.size() * sizeof(double));
 }
 int qdsp_hip_deemp_get_alpha(void* h, int chan, float* alpha) {
     Deemp* d = as_deemp(h);

@@ -6,7 +6,7 @@
 //   recurrence instead: tests/test_gpu_deemp.py).
 //   Tile = kDemodNT lanes x kDemodSpl consecutive samples.  A lane folds its samples into one pair; the 64 pairs of a wave are
 //   scanned by cross-lane moves; the four wave totals go through a few LDS words (one barrier pair per tile); the lane replays its
-//   samples from its exclusive prefix.
+//   samples from its exclusive prefix.  The scan of a tile and the tiles -> chunks geometry are scan.hip.h (cagc.hip uses them too).
 //     deemp_row_kernel      short rows, one launch: one workgroup per channel walks the row tile by tile
 //     deemp_partial_kernel  long rows, pass 1: workgroup g folds the T tiles of chunk g into one FP64 pair (the last chunk is skipped:
 //                           nothing follows it)
@@ -39,31 +39,19 @@ struct DeempArgs {
 
 namespace qh {
 
-constexpr uint32_t kDeempMagic = 0x51444545u;  // "QDEE"
-struct Deemp {
-    uint32_t magic = kDeempMagic;
-    int device = 0;
+struct Deemp : StreamOp {
+    Deemp() : StreamOp(kDeempMagic) {}
     int kind = 0;                          // QDSP_HIP_DEEMP_MONO / _STEREO
-    int nchan = 1;
     bool bypass = false;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
     double* d_state[2] = {nullptr, nullptr};
     int cur = 0;
     float* d_alpha = nullptr;
     std::vector<float> alpha;
     double* d_part = nullptr;
-    Launch last;
 };
 inline Deemp* as_deemp(void* h) {
     Deemp* d = static_cast<Deemp*>(h);
     return (d && d->magic == kDeempMagic) ? d : nullptr;
 }
-int deemp_time(Deemp* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 
 }  // namespace qh

@@ -203,40 +203,28 @@ void demod_free(Demod* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {d->d_in, d->d_out, (void*)d->d_phase[0], (void*)d->d_phase[1], (void*)d->d_speed, (void*)d->d_part})
+    for (void* p : {(void*)d->d_phase[0], (void*)d->d_phase[1], (void*)d->d_speed, (void*)d->d_part})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->nco) destroy(d->nco);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
+int demod_launch(Demod* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
+
 int demod_new(void** h, int device, int kind, int nchan, int max_block) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
-    if (kind < 0 || kind > kDemodSsb || nchan < 1 || nchan > kDemodMaxChan || max_block < 0) return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (h) *h = nullptr;
+    if (kind < 0 || kind > kDemodSsb) return QDSP_HIP_EINVAL;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     Demod* d = new (std::nothrow) Demod();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
     d->kind = kind;
-    d->nchan = nchan;
-    d->max_block = max_block;
+    d->launch = launch_as<Demod, demod_launch>;
     // phasorSpeed of sampleRate == deviation until set_fm: out = phase step / (2 pi)
     d->rate.assign(nchan, 1.0f);
     d->dev.assign(nchan, 1.0f);
     d->speed.assign(nchan, (2 * 3.1415926535f) / (1.0f / 1.0f));
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    const size_t in_b = (size_t)max_block * sizeof(float2), out_b = (size_t)max_block * out_floats(d) * sizeof(float);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, in_b);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, out_b);
+    hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float2), out_floats(d) * sizeof(float));
     if (is_fm(d)) {
         for (int i = 0; i < 2 && err == hipSuccess; i++) {
             err = hipMalloc(&d->d_phase[i], (size_t)nchan * sizeof(float));
@@ -327,69 +315,11 @@ int demod_launch(Demod* d, const void* d_in, int64_t count, int64_t in_stride, v
     return 0;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
-int demod_process_ex(Demod* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, (size_t)count * sizeof(float2), hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    const size_t out_bytes = (size_t)count * out_floats(d) * sizeof(float);
-    int rc = demod_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
-    if (rc) return rc;
-    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        // the consumer waits for done_ev (stream<T>::read); a pipelined input has been ordered on the shared stream already
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return 0;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return 0;
-}
-
-bool chan_ok(const Demod* d, int chan) { return chan >= 0 && chan < d->nchan; }
 }  // namespace
 
 // fm_demod_kernel with float rows out, for a caller that keeps its own phase slots (stereo_fm.hip): the launch alone
 void launch_fm_mono(const qk::FmArgs& a, int tiles, int nchan, hipStream_t s) {
     hipLaunchKernelGGL((qk::fm_demod_kernel<false>), dim3((unsigned)tiles, (unsigned)nchan), dim3(qk::kDemodNT), 0, s, a);
-}
-
-int demod_time(Demod* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int rc = demod_launch(d, d_in, count, count, d_out, count, s);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
 }
 
 }  // namespace qh
@@ -409,20 +339,16 @@ int qdsp_hip_demod_set_fm(void* h, int chan, float sample_rate, float deviation)
     // FloatFMDemod::init / setSampleRate / setDeviation (demodulator.h:42,62,72), in float
     const float speed = (2 * 3.1415926535f) / (sample_rate / deviation);
     if (!std::isfinite(sample_rate) || !std::isfinite(deviation) || !std::isfinite(speed) || speed == 0.0f) return QDSP_HIP_EINVAL;
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) {
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
         d->rate[c] = sample_rate;
         d->dev[c] = deviation;
         d->speed[c] = speed;
     }
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
-    HIPCHK(hipMemcpy(d->d_speed, d->speed.data(), (size_t)d->nchan * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    return sync_upload(d, d->d_speed, d->speed.data(), (size_t)d->nchan * sizeof(float));
 }
 int qdsp_hip_demod_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Demod* d = as_kind(h, false);
-    return d ? demod_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_demod_process(void* h, const float* in_iq, int count, void* out) {
     return qdsp_hip_demod_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
@@ -439,20 +365,13 @@ int qdsp_hip_demod_process_batch_dev(void* h, const void* d_in, int64_t count, i
 int qdsp_hip_demod_get_phase(void* h, int chan, float* phase) {
     Demod* d = as_kind(h, false);
     if (!d || !is_fm(d) || !chan_ok(d, chan) || !phase) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(phase, d->d_phase[d->cur] + chan, sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return sync_download(d, phase, d->d_phase[d->cur] + chan, sizeof(float));
 }
 int qdsp_hip_demod_set_phase(void* h, int chan, float phase) {
     Demod* d = as_kind(h, false);
     if (!d || !is_fm(d) || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    const int c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
-    std::vector<float> v((size_t)n, phase);
-    HIPCHK(hipMemcpy(d->d_phase[d->cur] + c0, v.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    const std::vector<float> v((size_t)chan_count(d, chan), phase);
+    return sync_upload(d, d->d_phase[d->cur] + chan_first(chan), v.data(), v.size() * sizeof(float));
 }
 int qdsp_hip_demod_reset(void* h) {
     Demod* d = as_kind(h, false);
@@ -484,7 +403,7 @@ int qdsp_hip_ssb_cf32_create(void** h, int device, float phase_inc_re, float pha
 }
 int qdsp_hip_ssb_cf32_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Demod* d = as_kind(h, true);
-    return d ? demod_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ssb_cf32_process(void* h, const float* in_iq, int count, float* out) {
     return qdsp_hip_ssb_cf32_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);

@@ -93,22 +93,12 @@ template <int NC> __device__ __forceinline__ void store_lane(float* row, long lo
 
 namespace qh {
 
-// the demodulator handle (FM, FM stereo, AM, and SSB around an xlator engine); misc_ops.hip's harness helpers take it too
-constexpr uint32_t kDemodMagic = 0x51444d44u;  // "QDMD"
+// the demodulator handle (FM, FM stereo, AM, and SSB around an xlator engine); misc_ops.hip's harness helpers take it as the
+// StreamOp it begins with (stream_op.h)
 constexpr int kDemodSsb = 3;                   // (QDSP_HIP_DEMOD_FM / _FM_STEREO / _AM are 0..2)
-constexpr int kDemodMaxChan = 65535;           // grid.y
-struct Demod {
-    uint32_t magic = kDemodMagic;
-    int device = 0;
+struct Demod : StreamOp {
+    Demod() : StreamOp(kDemodMagic) {}
     int kind = 0;
-    int nchan = 1;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;     // process_ex: the stream of the previous call
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
     // FM: carried phase, double-buffered (lanes of one launch read slot cur, the last sample's lane writes cur ^ 1)
     float* d_phase[2] = {nullptr, nullptr};
     int cur = 0;
@@ -118,13 +108,11 @@ struct Demod {
     double* d_part = nullptr;
     // SSB: the NCO state of an xlate_cf32 engine (never launched through the engine itself)
     Engine* nco = nullptr;
-    Launch last;
 };
 inline Demod* as_demod(void* h) {
     Demod* d = static_cast<Demod*>(h);
     return (d && d->magic == kDemodMagic) ? d : nullptr;
 }
-int demod_time(Demod* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 void launch_fm_mono(const qk::FmArgs& a, int tiles, int nchan, hipStream_t s);
 
 }  // namespace qh

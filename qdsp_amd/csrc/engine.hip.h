@@ -4,6 +4,9 @@
 //   chan_ops.hip   the channelizer (Splitter -> N x VFO as one operator): uniform polyphase plan, batched per-channel kernels,
 //                  qdsp_hip_chan_cf32_*
 //   misc_ops.hip   element-wise math blocks (src/dsp/math.h), synthetic IQ, events, the timing / introspection helpers
+//   stream_op.cpp  host only (stream_op.h): the handle head, creation / release, *_process_ex and timing of the per-row operators
+//                  (demod / deemp / level / stereo_fm / ff_agc / cagc / costas .hip, each with its kernels and its launch), and the
+//                  waits and the shared stream of every host path.  scan.hip.h: the tile scan of deemp.hip and cagc.hip
 // Everything here lives in namespace qh (internal: nothing of it is declared in include/qdsp_hip.h).
 #pragma once
 #include "../../include/qdsp_hip.h"
@@ -15,6 +18,7 @@
 #include "rm_resamp.hip.h"
 #include "fir_lat.hip.h"
 #include "knobs.h"
+#include "stream_op.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,22 +31,10 @@
 
 namespace qh {
 
-
-#define HIPCHK(expr)                                   \
-    do {                                               \
-        hipError_t e_ = (expr);                        \
-        if (e_ != hipSuccess) return -(int)e_;         \
-    } while (0)
-
 constexpr int kMaxDynLds = 64 * 1024;  // default dynamic-LDS ceiling; tiles are sized under it
 
 enum Kind : int { KIND_FIR = 1, KIND_DECIM = 2, KIND_XLATE = 3, KIND_VFO = 4, KIND_CHAN = 5, KIND_SINE = 6 };
 constexpr uint32_t kMagic = 0x51445350u;  // "QDSP"
-
-struct Launch {
-    const char* name = "";
-    int grid = 0, block = 0, lds = 0;
-};
 
 // One engine serves FIR, resampler, xlator and the fused VFO: they differ only in
 // (ch, interp, decim, rotate) and in which kernel the launch picks.
@@ -178,11 +170,8 @@ inline Chan* as_chan(void* h) {
     return (c && c->magic == kChanMagic) ? c : nullptr;
 }
 
-// ---- shared by the translation units (defined in qdsp_hip.hip) ----
+// ---- shared by the translation units (defined in qdsp_hip.hip; wait_stream, wait_event, shared_stream and mapped_host_ptr: stream_op.h) ----
 Engine* as_engine(void* h, Kind k);
-hipError_t wait_stream(hipStream_t s);
-hipError_t wait_event(hipEvent_t ev, hipStream_t s);
-hipStream_t shared_stream(int device);
 long double turns_of(float re, float im);
 unsigned long long fx_of_turns(long double t);
 void unit_of_fx(unsigned long long ph, long double mult, double* c, double* s);
@@ -231,7 +220,6 @@ int64_t mf_min_count(const Engine* e);
 int64_t rm_min_count(const Engine* e);
 int64_t process_dev(Engine* e, const void* d_in, int64_t count, void* d_out, void* stream);
 int64_t process_host(Engine* e, const float* in, int count, float* out);
-void* mapped_host_ptr(void* p);
 int64_t process_ex(Engine* e, const void* in, int in_dev, int count, void* out, int out_dev);
 int reset(Engine* e);
 int get_history(Engine* e, float* hist);

@@ -166,7 +166,8 @@ namespace {
 int comps(const FfAgc* d) { return d->kind == qk::kFfAgcComplex ? 2 : 1; }
 int hstride(const FfAgc* d) { return d->window > 1 ? d->window - 1 : 1; }
 size_t hist_bytes(const FfAgc* d) { return (size_t)d->nchan * hstride(d) * comps(d) * sizeof(float); }
-int64_t out_count(const FfAgc* d, int64_t count) {
+int64_t out_count(const StreamOp* op, int64_t count) {   // (StreamOp::out_count)
+    const FfAgc* d = static_cast<const FfAgc*>(op);
     const int64_t n = (int64_t)d->fill + count - (d->window - 1);
     return n > 0 ? n : 0;
 }
@@ -175,37 +176,26 @@ void ffagc_free(FfAgc* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {d->d_in, d->d_out, (void*)d->d_hist[0], (void*)d->d_hist[1]})
+    for (void* p : {(void*)d->d_hist[0], (void*)d->d_hist[1]})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
+int64_t ffagc_launch(FfAgc* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
+
 int ffagc_new(void** h, int device, int kind, int nchan, int max_block, int window) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
+    if (h) *h = nullptr;
     if (kind != QDSP_HIP_FFAGC_REAL && kind != QDSP_HIP_FFAGC_COMPLEX) return QDSP_HIP_EINVAL;
-    if (nchan < 1 || nchan > kDemodMaxChan || max_block < 0 || window < 1 || window > qk::kFfAgcMaxWindow) return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (window < 1 || window > qk::kFfAgcMaxWindow) return QDSP_HIP_EINVAL;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     FfAgc* d = new (std::nothrow) FfAgc();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
     d->kind = kind;
-    d->nchan = nchan;
-    d->max_block = max_block;
     d->window = window;
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    const size_t io_b = (size_t)max_block * comps(d) * sizeof(float);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, io_b);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, io_b);
+    d->launch = launch_as<FfAgc, ffagc_launch>;
+    d->out_count = out_count;
+    hipError_t err = stream_op_init(d, device, nchan, max_block, comps(d) * sizeof(float), comps(d) * sizeof(float));
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_hist[i], hist_bytes(d));
         if (err == hipSuccess) err = hipMemset(d->d_hist[i], 0, hist_bytes(d));
@@ -271,65 +261,7 @@ int64_t ffagc_launch(FfAgc* d, const void* d_in, int64_t count, int64_t in_strid
     return nout;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel.  Returns the output count.
-int ffagc_process_ex(FfAgc* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && !in)) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    const int64_t nout = out_count(d, count);
-    if (nout > 0 && !out) return QDSP_HIP_EINVAL;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const size_t es = (size_t)comps(d) * sizeof(float);
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, (size_t)count * es, hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    const int64_t rc = ffagc_launch(d, src, count, count, out_host ? d->d_out : out, nout, st);
-    if (rc < 0) return (int)rc;
-    if (out_host && nout > 0) HIPCHK(hipMemcpyAsync(out, d->d_out, (size_t)nout * es, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return (int)nout;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return (int)nout;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return (int)nout;
-}
 }  // namespace
-
-// (d_out holds the outputs of the longest of the calls: `count` samples per row are enough)
-int ff_agc_time(FfAgc* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int64_t rc = ffagc_launch(d, d_in, count, count, d_out, count, s);
-        if (rc < 0) return (int)rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
-}
 
 }  // namespace qh
 
@@ -342,7 +274,7 @@ int qdsp_hip_ffagc_create(void** h, int device, int kind, int nchan, int max_blo
 }
 int qdsp_hip_ffagc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     FfAgc* d = as_ff_agc(h);
-    return d ? ffagc_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ffagc_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_ffagc_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);

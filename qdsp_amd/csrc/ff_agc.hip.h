@@ -62,29 +62,17 @@ constexpr int ff_agc_lds(int W) { return 2 * ff_agc_L(W) * (int)sizeof(float); }
 
 namespace qh {
 
-constexpr uint32_t kFfAgcMagic = 0x51464147u;  // "QFAG"
-struct FfAgc {
-    uint32_t magic = kFfAgcMagic;
-    int device = 0;
+struct FfAgc : StreamOp {
+    FfAgc() : StreamOp(kFfAgcMagic) {}
     int kind = 0;                          // qk::kFfAgcReal / kFfAgcComplex
-    int nchan = 1;
     int window = 1024;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
     float* d_hist[2] = {nullptr, nullptr}; // read from slot cur, written to cur ^ 1
     int cur = 0;
     int fill = 0;                          // samples held, the same for every row
-    Launch last;
 };
 inline FfAgc* as_ff_agc(void* h) {
     FfAgc* d = static_cast<FfAgc*>(h);
     return (d && d->magic == kFfAgcMagic) ? d : nullptr;
 }
-int ff_agc_time(FfAgc* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 
 }  // namespace qh

@@ -146,7 +146,6 @@ namespace qh {
 
 namespace {
 int comps(const Level* d) { return d->kind == qk::kLevelSquelch ? 2 : 1; }
-bool chan_ok(const Level* d, int chan) { return chan >= 0 && chan < d->nchan; }
 Level* as_kind(void* h, int kind) {
     Level* d = as_level(h);
     return (d && d->kind == kind) ? d : nullptr;
@@ -156,38 +155,25 @@ void level_free(Level* d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {d->d_in, d->d_out, d->d_state[0], d->d_state[1], (void*)d->d_param, (void*)d->d_part})
+    for (void* p : {d->d_state[0], d->d_state[1], (void*)d->d_param, (void*)d->d_part})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
+int level_launch(Level* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
+
 int level_new(void** h, int device, int kind, int nchan, int max_block, float param0) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
-    if (nchan < 1 || nchan > kDemodMaxChan || max_block < 0) return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (h) *h = nullptr;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     Level* d = new (std::nothrow) Level();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
     d->kind = kind;
-    d->nchan = nchan;
-    d->max_block = max_block;
+    d->launch = launch_as<Level, level_launch>;
     d->param.assign(nchan, param0);
     d->fall.assign(nchan, 0.0f);
     d->rate.assign(nchan, 1.0f);
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    const size_t io_b = (size_t)max_block * comps(d) * sizeof(float);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, io_b);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, io_b);
+    hipError_t err = stream_op_init(d, device, nchan, max_block, comps(d) * sizeof(float), comps(d) * sizeof(float));
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_state[i], (size_t)nchan * 4);
         if (err == hipSuccess) err = hipMemset(d->d_state[i], 0, (size_t)nchan * 4);   // level 0.0f / closed
@@ -204,12 +190,8 @@ int level_new(void** h, int device, int kind, int nchan, int max_block, float pa
 }
 
 int push_param(Level* d, int chan, float v) {
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) d->param[c] = v;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
-    HIPCHK(hipMemcpy(d->d_param, d->param.data(), (size_t)d->nchan * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) d->param[c] = v;
+    return sync_upload(d, d->d_param, d->param.data(), (size_t)d->nchan * sizeof(float));
 }
 
 template <int KIND> void launch_kind(const qk::LevelArgs& a, bool row, int nchan, hipStream_t s) {
@@ -266,52 +248,8 @@ int level_launch(Level* d, const void* d_in, int64_t count, int64_t in_stride, v
     return 0;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
-int level_process_ex(Level* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const size_t bytes = (size_t)count * comps(d) * sizeof(float);
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    int rc = level_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
-    if (rc) return rc;
-    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, bytes, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return 0;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return 0;
-}
-
 // one 4-byte state word of channel `chan` (slot cur), after everything queued has run
-int get_state(Level* d, int chan, void* v) {
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(v, static_cast<char*>(d->d_state[d->cur]) + (size_t)chan * 4, 4, hipMemcpyDeviceToHost));
-    return 0;
-}
+int get_state(Level* d, int chan, void* v) { return sync_download(d, v, static_cast<char*>(d->d_state[d->cur]) + (size_t)chan * 4, 4); }
 
 int level_reset(Level* d) {
     HIPCHK(hipSetDevice(d->device));
@@ -320,23 +258,6 @@ int level_reset(Level* d) {
     return 0;
 }
 }  // namespace
-
-int level_time(Level* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int rc = level_launch(d, d_in, count, count, d_out, count, s);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
-}
 
 }  // namespace qh
 
@@ -360,7 +281,7 @@ int qdsp_hip_squelch_get_open(void* h, int chan, int* open) {
 }
 int qdsp_hip_squelch_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Level* d = as_kind(h, qk::kLevelSquelch);
-    return d ? level_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_squelch_process(void* h, const float* in_iq, int count, float* out_iq) {
     return qdsp_hip_squelch_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out_iq, QDSP_HIP_LINK_HOST);
@@ -388,8 +309,7 @@ int qdsp_hip_agc_set(void* h, int chan, float fall_rate, float sample_rate) {
     Level* d = as_kind(h, qk::kLevelAgc);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (!std::isfinite(sample_rate) || sample_rate <= 0.0f || !std::isfinite(fall_rate)) return QDSP_HIP_EINVAL;
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) {
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
         d->fall[c] = fall_rate;
         d->rate[c] = sample_rate;
     }
@@ -403,16 +323,12 @@ int qdsp_hip_agc_get_level(void* h, int chan, float* level) {
 int qdsp_hip_agc_set_level(void* h, int chan, float level) {
     Level* d = as_kind(h, qk::kLevelAgc);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    const int c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
-    std::vector<float> v((size_t)n, level);
-    HIPCHK(hipMemcpy(static_cast<float*>(d->d_state[d->cur]) + c0, v.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    const std::vector<float> v((size_t)chan_count(d, chan), level);
+    return sync_upload(d, static_cast<float*>(d->d_state[d->cur]) + chan_first(chan), v.data(), v.size() * sizeof(float));
 }
 int qdsp_hip_agc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     Level* d = as_kind(h, qk::kLevelAgc);
-    return d ? level_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_agc_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_agc_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);

@@ -63,31 +63,19 @@ __device__ __forceinline__ float agc_level(float level, float cfr, long long cou
 
 namespace qh {
 
-constexpr uint32_t kLevelMagic = 0x514c564cu;  // "QLVL"
-struct Level {
-    uint32_t magic = kLevelMagic;
-    int device = 0;
+struct Level : StreamOp {
+    Level() : StreamOp(kLevelMagic) {}
     int kind = 0;                          // qk::kLevelSquelch / kLevelAgc
-    int nchan = 1;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
     void* d_state[2] = {nullptr, nullptr}; // 4 bytes per channel
     int cur = 0;
     float* d_param = nullptr;
     std::vector<float> param;              // Squelch: level; AGC: fall / rate
     std::vector<float> fall, rate;         // AGC
     double* d_part = nullptr;
-    Launch last;
 };
 inline Level* as_level(void* h) {
     Level* d = static_cast<Level*>(h);
     return (d && d->magic == kLevelMagic) ? d : nullptr;
 }
-int level_time(Level* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 
 }  // namespace qh

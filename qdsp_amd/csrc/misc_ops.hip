@@ -1,12 +1,7 @@
 // misc_ops.hip -- the element-wise two-input blocks of src/dsp/math.h (Add / Substract / Multiply), the synthetic IQ source of the
 // bench, completion events and the timing / introspection helpers of the harness.  Split out of qdsp_hip.hip in round 3.
 #include "engine.hip.h"
-#include "deemp.hip.h"
-#include "level.hip.h"
-#include "stereo_fm.hip.h"
-#include "ff_agc.hip.h"
-#include "cagc.hip.h"
-#include "costas.hip.h"
+#include "stream_op.h"
 
 namespace qh {
 
@@ -169,31 +164,7 @@ int qdsp_hip_event_wait(void* ev) {
     return 0;
 }
 int qdsp_hip_set_done_event(void* h, void* ev) {
-    if (Demod* d = as_demod(h)) {
-        d->done_ev = static_cast<hipEvent_t>(ev);
-        return 0;
-    }
-    if (Deemp* d = as_deemp(h)) {
-        d->done_ev = static_cast<hipEvent_t>(ev);
-        return 0;
-    }
-    if (Level* d = as_level(h)) {
-        d->done_ev = static_cast<hipEvent_t>(ev);
-        return 0;
-    }
-    if (StereoFm* d = as_stereo_fm(h)) {
-        d->done_ev = static_cast<hipEvent_t>(ev);
-        return 0;
-    }
-    if (FfAgc* d = as_ff_agc(h)) {
-        d->done_ev = static_cast<hipEvent_t>(ev);
-        return 0;
-    }
-    if (Cagc* d = as_cagc(h)) {
-        d->done_ev = static_cast<hipEvent_t>(ev);
-        return 0;
-    }
-    if (Costas* d = as_costas(h)) {
+    if (StreamOp* d = as_stream_op(h)) {
         d->done_ev = static_cast<hipEvent_t>(ev);
         return 0;
     }
@@ -206,13 +177,7 @@ int qdsp_hip_set_done_event(void* h, void* ev) {
 int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* block, int* lds) {
     const Launch* l = nullptr;
     if (Chan* c = as_chan(h)) l = &c->last;
-    else if (Demod* d = as_demod(h)) l = &d->last;
-    else if (Deemp* d = as_deemp(h)) l = &d->last;
-    else if (Level* d = as_level(h)) l = &d->last;
-    else if (StereoFm* d = as_stereo_fm(h)) l = &d->last;
-    else if (FfAgc* d = as_ff_agc(h)) l = &d->last;
-    else if (Cagc* d = as_cagc(h)) l = &d->last;
-    else if (Costas* d = as_costas(h)) l = &d->last;
+    else if (StreamOp* d = as_stream_op(h)) l = &d->last;
     else if (Engine* e = any_engine(h)) l = &e->last;
     if (!l) return QDSP_HIP_EINVAL;
     if (name && name_len > 0) { strncpy(name, l->name, name_len - 1); name[name_len - 1] = 0; }
@@ -223,13 +188,7 @@ int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* bloc
 }
 
 int qdsp_hip_time_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (Demod* d = as_demod(h)) return demod_time(d, d_in, count, d_out, stream, iters, ms);
-    if (Deemp* d = as_deemp(h)) return deemp_time(d, d_in, count, d_out, stream, iters, ms);
-    if (Level* d = as_level(h)) return level_time(d, d_in, count, d_out, stream, iters, ms);
-    if (StereoFm* d = as_stereo_fm(h)) return stereo_fm_time(d, d_in, count, d_out, stream, iters, ms);
-    if (FfAgc* d = as_ff_agc(h)) return ff_agc_time(d, d_in, count, d_out, stream, iters, ms);
-    if (Cagc* d = as_cagc(h)) return cagc_time(d, d_in, count, d_out, stream, iters, ms);
-    if (Costas* d = as_costas(h)) return costas_time(d, d_in, count, d_out, stream, iters, ms);
+    if (StreamOp* d = as_stream_op(h)) return stream_op_time(d, d_in, count, d_out, stream, iters, ms);
     Engine* e = any_engine(h);
     return e ? time_process(e, d_in, count, d_out, stream, iters, ms) : QDSP_HIP_EINVAL;
 }

@@ -15,59 +15,6 @@ Engine* as_engine(void* h, Kind k) {
     return e;
 }
 
-// End-of-call wait of the host-pointer paths.  hipStreamSynchronize sleeps on an interrupt (~20 us to wake up),
-// longer than the kernels of a reference-sized block take: poll the stream for a bounded time first
-// (QDSP_HIP_SYNC_SPIN_US, default 200; 0 = always block).
-hipError_t wait_stream(hipStream_t s) {
-    static const int spin_us = 200;
-    if (spin_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        do {
-            const hipError_t q = hipStreamQuery(s);
-            if (q == hipSuccess) return hipSuccess;
-            if (q != hipErrorNotReady) return q;
-        } while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(spin_us));
-    }
-    return hipStreamSynchronize(s);
-}
-
-// The same for the library's shared stream: wait for THIS call's work only (an event recorded behind it), not for
-// whatever the upstream blocks have queued for later blocks in the meantime.
-hipError_t wait_event(hipEvent_t ev, hipStream_t s) {
-    hipError_t rc = hipEventRecord(ev, s);
-    if (rc != hipSuccess) return rc;
-    static const int spin_us = 200;
-    if (spin_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        do {
-            const hipError_t q = hipEventQuery(ev);
-            if (q == hipSuccess) return hipSuccess;
-            if (q != hipErrorNotReady) return q;
-        } while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(spin_us));
-    }
-    return hipEventSynchronize(ev);
-}
-
-// (Ordering the two ends of a link with events instead -- every handle on its own stream, two events per device
-// buffer of the stream<T>, hipStreamWaitEvent before and hipEventRecord behind each kernel -- was built and
-// measured: the cross-stream dependencies cost more than the serialisation they remove; SineSource -> VFO 23 -> 27 us
-// per block, Splitter -> 4 / 16 x VFO 80 -> 120 / 386 -> 615 us.)
-// One in-order stream per device for "pipelined" device-resident links (QDSP_HIP_LINK_PIPELINED): a producer
-// launches into it and hands its block over without waiting; the consumer launches into the same stream, so
-// the GPU runs the two in launch order -- which is the order the stream<T> protocol imposes on the host threads
-// (the consumer reads a block only after the producer swapped it in, the producer reuses a buffer only after
-// the consumer flushed it, and both launch before they swap / flush).
-hipStream_t shared_stream(int device) {
-    static std::mutex m;
-    static hipStream_t tab[64] = {};
-    std::lock_guard<std::mutex> lk(m);
-    if (device < 0 || device >= 64) return nullptr;
-    if (!tab[device]) {
-        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&tab[device], hipStreamNonBlocking) != hipSuccess) tab[device] = nullptr;
-    }
-    return tab[device];
-}
-
 long double turns_of(float re, float im) {
     // arg(phase_inc)/2pi in [0,1): the angle the reference's recursive phasor actually
     // advances by each sample is that of the ROUNDED float pair, not of the ideal theta.
@@ -1967,16 +1914,6 @@ int64_t process_host(Engine* e, const float* in, int count, float* out) {
         HIPCHK(hipMemcpyAsync(out, e->d_out, (size_t)nout * e->ch * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(wait_stream(e->stream));
     return nout;
-}
-
-// The device address of a pinned host buffer the kernels may store into, or nullptr (pageable memory).  Asked on
-// every call (~1 us): a remembered answer could outlive the buffer it was about.
-void* mapped_host_ptr(void* p) {
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) return at.devicePointer;
-    (void)hipGetLastError();   // (pageable memory: an error the runtime keeps otherwise)
-    return nullptr;
 }
 
 // run() with each side on the host (pinned stream buffer) or already on the device (the

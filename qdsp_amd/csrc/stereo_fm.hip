@@ -124,7 +124,6 @@ __global__ __launch_bounds__(kDemodNT) void stereo_mix_kernel(const MixArgs a) {
 namespace qh {
 
 namespace {
-bool chan_ok(const StereoFm* d, int chan) { return chan >= 0 && chan < d->nchan; }
 size_t hist_floats(const StereoFm* d) { return (size_t)d->nchan * (size_t)(d->ntaps > 1 ? d->ntaps - 1 : 1); }
 
 void free_scratch(StereoFm* d) {
@@ -140,13 +139,10 @@ void sfm_free(StereoFm* d) {
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
     free_scratch(d);
-    for (void* p : {d->d_in, d->d_out, (void*)d->d_phase[0], (void*)d->d_phase[1], (void*)d->d_hist[0], (void*)d->d_hist[1],
-                    (void*)d->d_level[0], (void*)d->d_level[1], (void*)d->d_speed, (void*)d->d_cfr, (void*)d->d_taps})
+    for (void* p : {(void*)d->d_phase[0], (void*)d->d_phase[1], (void*)d->d_hist[0], (void*)d->d_hist[1], (void*)d->d_level[0],
+                    (void*)d->d_level[1], (void*)d->d_speed, (void*)d->d_cfr, (void*)d->d_taps})
         if (p) (void)hipFree(p);
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    d->magic = 0;
+    stream_op_release(d);
     delete d;
 }
 
@@ -193,28 +189,20 @@ hipError_t load_taps(StereoFm* d, const float* taps, int ntaps) {
     return err;
 }
 
+int sfm_launch(StereoFm* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
+
 int sfm_new(void** h, int device, int nchan, const float* taps, int ntaps, int max_block) {
-    if (!h) return QDSP_HIP_EINVAL;
-    *h = nullptr;
-    if (nchan < 1 || nchan > kDemodMaxChan || max_block < 0 || !taps || ntaps < 1 || ntaps > qk::kPilotMaxTaps) return QDSP_HIP_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return QDSP_HIP_ENODEV;
-    if (device < 0 || device >= ndev) return QDSP_HIP_ENODEV;
-    HIPCHK(hipSetDevice(device));
+    if (h) *h = nullptr;
+    if (!taps || ntaps < 1 || ntaps > qk::kPilotMaxTaps) return QDSP_HIP_EINVAL;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
     StereoFm* d = new (std::nothrow) StereoFm();
     if (!d) return QDSP_HIP_ENOMEM;
-    d->device = device;
-    d->nchan = nchan;
-    d->max_block = max_block;
+    d->launch = launch_as<StereoFm, sfm_launch>;
     // sampleRate == deviation == 1 until set_fm
     d->speed.assign(nchan, (2 * 3.1415926535f) / (1.0f / 1.0f));
     d->cfr.assign(nchan, 20.0f / 1.0f);
     const size_t per_chan = (size_t)nchan * sizeof(float);
-    hipError_t err = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&d->ev1);
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_in, (size_t)max_block * sizeof(float2));
-    if (err == hipSuccess && max_block > 0) err = hipMalloc(&d->d_out, (size_t)max_block * sizeof(float2));
+    hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float2), sizeof(float2));
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_phase[i], per_chan);
         if (err == hipSuccess) err = hipMemset(d->d_phase[i], 0, per_chan);
@@ -304,78 +292,13 @@ int sfm_launch(StereoFm* d, const void* d_in, int64_t count, int64_t in_stride, 
     return 0;
 }
 
-// run() with each side on the host or the device (link codes as for every *_process_ex); one channel
-int sfm_process_ex(StereoFm* d, const void* in, int in_link, int count, void* out, int out_link) {
-    if (d->nchan != 1 || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
-    if (in_link < QDSP_HIP_LINK_HOST || in_link > QDSP_HIP_LINK_PIPELINED || out_link < QDSP_HIP_LINK_HOST ||
-        out_link > QDSP_HIP_LINK_HOST_DEFERRED)
-        return QDSP_HIP_EINVAL;
-    const bool deferred = out_link == QDSP_HIP_LINK_HOST_DEFERRED;
-    if (deferred && !d->done_ev) return QDSP_HIP_EINVAL;
-    const bool out_host = out_link == QDSP_HIP_LINK_HOST || deferred;
-    if ((in_link == QDSP_HIP_LINK_HOST || out_host) && count > d->max_block) return QDSP_HIP_ESIZE;
-    if (count == 0) return 0;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t st = d->stream;
-    if (in_link == QDSP_HIP_LINK_PIPELINED || out_link == QDSP_HIP_LINK_PIPELINED) {
-        st = shared_stream(d->device);
-        if (!st) return QDSP_HIP_ENOMEM;
-    }
-    if (d->last_stream && d->last_stream != st) HIPCHK(hipStreamSynchronize(d->last_stream));   // (links re-plumbed)
-    d->last_stream = st;
-    const size_t bytes = (size_t)count * sizeof(float2);
-    const void* src = in;
-    if (in_link == QDSP_HIP_LINK_HOST) {
-        HIPCHK(hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, st));
-        src = d->d_in;
-    }
-    int rc = sfm_launch(d, src, count, count, out_host ? d->d_out : out, count, st);
-    if (rc) return rc;
-    if (out_host) HIPCHK(hipMemcpyAsync(out, d->d_out, bytes, hipMemcpyDeviceToHost, st));
-    if (deferred) {
-        HIPCHK(hipEventRecord(d->done_ev, st));
-        if (in_link == QDSP_HIP_LINK_PIPELINED && mapped_host_ptr(out)) return 0;
-        HIPCHK(hipEventSynchronize(d->done_ev));
-        return 0;
-    }
-    if (!(out_link == QDSP_HIP_LINK_PIPELINED && in_link == QDSP_HIP_LINK_PIPELINED))
-        HIPCHK(st == d->stream ? wait_stream(st) : wait_event(d->ev0, st));
-    return 0;
-}
-
 // one float of channel `chan` of a double-buffered state (slot cur), after everything queued has run
-int get_word(StereoFm* d, float* const* slots, int chan, float* v) {
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(v, slots[d->cur] + chan, sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
+int get_word(StereoFm* d, float* const* slots, int chan, float* v) { return sync_download(d, v, slots[d->cur] + chan, sizeof(float)); }
 int set_word(StereoFm* d, float* const* slots, int chan, float v) {
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());
-    const int c0 = chan < 0 ? 0 : chan, n = chan < 0 ? d->nchan : 1;
-    std::vector<float> w((size_t)n, v);
-    HIPCHK(hipMemcpy(slots[d->cur] + c0, w.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    const std::vector<float> w((size_t)chan_count(d, chan), v);
+    return sync_upload(d, slots[d->cur] + chan_first(chan), w.data(), w.size() * sizeof(float));
 }
 }  // namespace
-
-int stereo_fm_time(StereoFm* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms) {
-    if (iters <= 0 || !ms) return QDSP_HIP_EINVAL;
-    HIPCHK(hipSetDevice(d->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipEventRecord(d->ev0, s));
-    for (int i = 0; i < iters; i++) {
-        const int rc = sfm_launch(d, d_in, count, count, d_out, count, s);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(d->ev1, s));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float t = 0.0f;
-    HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-    *ms = t / (float)iters;
-    return 0;
-}
 
 }  // namespace qh
 
@@ -394,14 +317,11 @@ int qdsp_hip_stereo_fm_set_fm(void* h, int chan, float sample_rate, float deviat
     const float cfr = 20.0f / sample_rate;
     if (!std::isfinite(sample_rate) || sample_rate <= 0.0f || !std::isfinite(deviation) || !std::isfinite(speed) || speed == 0.0f)
         return QDSP_HIP_EINVAL;
-    const int c0 = chan < 0 ? 0 : chan, c1 = chan < 0 ? d->nchan : chan + 1;
-    for (int c = c0; c < c1; c++) {
+    for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
         d->speed[c] = speed;
         d->cfr[c] = cfr;
     }
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipDeviceSynchronize());   // (a launch in flight may still read the old values)
-    HIPCHK(hipMemcpy(d->d_speed, d->speed.data(), (size_t)d->nchan * sizeof(float), hipMemcpyHostToDevice));
+    if (const int rc = sync_upload(d, d->d_speed, d->speed.data(), (size_t)d->nchan * sizeof(float))) return rc;
     HIPCHK(hipMemcpy(d->d_cfr, d->cfr.data(), (size_t)d->nchan * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
@@ -415,7 +335,7 @@ int qdsp_hip_stereo_fm_set_pilot_taps(void* h, const float* taps, int ntaps) {
 }
 int qdsp_hip_stereo_fm_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
     StereoFm* d = as_stereo_fm(h);
-    return d ? sfm_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_stereo_fm_process(void* h, const float* in_iq, int count, float* out_lr) {
     return qdsp_hip_stereo_fm_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out_lr, QDSP_HIP_LINK_HOST);

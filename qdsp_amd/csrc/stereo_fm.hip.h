@@ -57,19 +57,9 @@ struct MixArgs {
 
 namespace qh {
 
-constexpr uint32_t kStereoFmMagic = 0x5153464du;  // "QSFM"
-struct StereoFm {
-    uint32_t magic = kStereoFmMagic;
-    int device = 0;
-    int nchan = 1;
+struct StereoFm : StreamOp {
+    StereoFm() : StreamOp(kStereoFmMagic) {}
     int ntaps = 0;
-    hipStream_t stream = nullptr;          // host-pointer path
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t done_ev = nullptr;          // QDSP_HIP_LINK_HOST_DEFERRED
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    int max_block = 0;
     float* d_phase[2] = {nullptr, nullptr};   // FM phase, history and level: read from slot cur, written to cur ^ 1
     float* d_hist[2] = {nullptr, nullptr};
     float* d_level[2] = {nullptr, nullptr};
@@ -83,12 +73,10 @@ struct StereoFm {
     double* d_part = nullptr;
     long long scratch_cap = 0;             // samples per row
     long long last_count = 0, last_sstride = 0;
-    Launch last;
 };
 inline StereoFm* as_stereo_fm(void* h) {
     StereoFm* d = static_cast<StereoFm*>(h);
     return (d && d->magic == kStereoFmMagic) ? d : nullptr;
 }
-int stereo_fm_time(StereoFm* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
 
 }  // namespace qh

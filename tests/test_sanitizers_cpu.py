@@ -6,7 +6,9 @@ the test pool and not wanted).
   the calling thread) built with -fsanitize=thread and with -fsanitize=address,undefined;
 * qdsp_amd/csrc/knobs.cpp: readers against concurrent reloads under -fsanitize=thread;
 * qdsp_amd/csrc/ring.cpp: the halo ring's buffer rotation against a fake synchronous HIP runtime + one-rank RCCL under
-  -fsanitize=address,undefined.
+  -fsanitize=address,undefined;
+* qdsp_amd/csrc/stream_op.cpp: the host path the per-row operators share (link codes, staging, error precedence, creation and
+  release) with a dummy operator on the same fake runtime, under -fsanitize=address,undefined.
 Pass = every program exits 0 and no sanitizer report appears on stderr."""
 import os
 import shutil
@@ -120,3 +122,18 @@ def test_halo_ring_bookkeeping_under_asan_ubsan():
                  "ring_selftest.cpp", os.path.join(ROOT, "qdsp_amd", "csrc", "ring.cpp"), f"-L{out}", "-lfakehip", "-ldl", "-Wl,-rpath,$ORIGIN"])
     env = {"LD_LIBRARY_PATH": out + os.pathsep + os.environ.get("LD_LIBRARY_PATH", "")}
     assert "ring ok" in run_clean([os.path.join(out, "ring_selftest")], cwd=out, extra_env=env)
+
+
+def test_stream_op_host_path_under_asan_ubsan():
+    """qdsp_amd/csrc/stream_op.cpp -- the handle head and the one *_process_ex of the per-row operators -- with a dummy operator on
+    the fake HIP runtime: every pair of link codes, the error codes and their precedence, timing, creation and release."""
+    hip_inc = "/opt/rocm/include"
+    if not os.path.exists(os.path.join(hip_inc, "hip", "hip_runtime.h")):
+        pytest.skip("needs the HIP headers")
+    out = os.path.join(FAKE, "build", "address_stream_op")
+    os.makedirs(out, exist_ok=True)
+    flags = BASE + ["-fsanitize=address,undefined"]
+    cxx(flags + ["-fPIC", "-shared", "-DFAKE_HIP", "-o", os.path.join(out, "libfakehip.so"), "fake_hip_runtime.cpp"])
+    cxx(flags + ["-Wall", "-D__HIP_PLATFORM_AMD__", f"-I{hip_inc}", "-o", os.path.join(out, "stream_op_selftest"), "stream_op_selftest.cpp",
+                 os.path.join(ROOT, "qdsp_amd", "csrc", "stream_op.cpp"), f"-L{out}", "-lfakehip", "-Wl,-rpath,$ORIGIN"])
+    assert "stream_op ok" in run_clean([os.path.join(out, "stream_op_selftest")], cwd=out)
