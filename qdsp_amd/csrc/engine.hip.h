@@ -56,7 +56,9 @@ struct Engine {
     bool volk_gain = true;     // emulate the VOLK rotator's magnitude sawtooth (see rotate())
     float gm1 = 0.0f;          // |phase_inc| - 1
     // device state
-    float* d_taps = nullptr;
+    float* d_taps = nullptr;       // core layout (branch-major, taps_core) or the phase table [L][P]
+    bool taps_core = false;        // the layout upload_taps() gave d_taps: the launch follows it, not QDSP_HIP_FORCE_ANY at call time
+    float* d_taps_plain = nullptr; // the phase table beside a core-layout d_taps, built by the first call that needs it (plain_taps)
     double2* d_nco_tab = nullptr;  // tile_phasor tables of the direct kernels (fused NCO)
     unsigned long long nco_key_dphase = 0;
     long long nco_key_S = 0;
@@ -89,6 +91,8 @@ struct Engine {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // overlap-save fast convolution (FIR<complex_t> with many taps), fft_fir.hip.h
     int fir_mode = 0;           // 0 auto, 1 direct form, 2 overlap-save FFT
+    // (both hold only while process_dev runs: it clears them on every way out, so that plan-time code -- upload_taps, mf_plan, chan_batch_wins --
+    // sees the rule chain alone and a handle's tables do not depend on the calls it has served)
     int auto_veto = 0, auto_mode = 0;   // integer decimators / fused VFO, AUTO: per-call exceptions to the rule chain named by the measured table (decim_table.inc)
     int auto_pick = 0;          // FIR<complex_t>, AUTO: the kernel family the measured table names for this call (dispatch_table.inc), 0 = the rule chain
     float2* d_fft_H = nullptr;  // spectrum of the reversed taps / F, digit-reversed

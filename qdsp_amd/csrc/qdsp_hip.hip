@@ -138,7 +138,9 @@ int upload_taps(Engine* e, const float* taps, int ntaps) {
     // resampler L==1: tapPhases[0][t] = taps[t]   -> core with M, Q=ceil(P/M), H=P
     // otherwise: [L][P] phase table, buildTapPhases (resampling.h:137-166)
     std::vector<float> host;
-    if (use_core(e)) {
+    e->taps_core = use_core(e);
+    if (e->d_taps_plain) { HIPCHK(hipFree(e->d_taps_plain)); e->d_taps_plain = nullptr; }
+    if (e->taps_core) {
         const int K = e->P;
         const int Q = (K + e->M - 1) / e->M;
         host.assign((size_t)e->M * Q, 0.0f);
@@ -325,11 +327,24 @@ int upload_taps(Engine* e, const float* taps, int ntaps) {
     return 0;
 }
 
+// The phase table [1][P] of a handle whose d_taps is branch-major (interp 1, decimation <= 8): what resamp_any_kernel reads when
+// QDSP_HIP_FORCE_ANY sends such a handle's call to it.  Built on first use, dropped with the taps.
+int plain_taps(Engine* e) {
+    if (e->d_taps_plain) return 0;
+    if ((int)e->taps_host.size() != e->P || e->L != 1) return QDSP_HIP_EINVAL;
+    HIPCHK(hipMalloc(&e->d_taps_plain, (size_t)e->P * sizeof(float)));
+    HIPCHK(hipMemcpy(e->d_taps_plain, e->taps_host.data(), (size_t)e->P * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
 // (Re)configure the filter part.  History keeps its newest samples across a resize.
 int configure(Engine* e, const float* taps, int ntaps, int interp, int decim) {
     if (!taps || ntaps <= 0 || interp <= 0 || decim <= 0) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipDeviceSynchronize());
+    e->auto_pick = 0;      // (plan with the rule chain alone: process_dev leaves these cleared as well)
+    e->auto_veto = 0;
+    e->auto_mode = 0;
     const int oldH = e->H;
     e->L = interp;
     e->M = decim;
@@ -447,6 +462,7 @@ void destroy(Engine* e) {
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
     if (e->d_taps) (void)hipFree(e->d_taps);
+    if (e->d_taps_plain) (void)hipFree(e->d_taps_plain);
     if (e->d_taps_lm) (void)hipFree(e->d_taps_lm);
     for (int i = 0; i < 2; i++)
         if (e->d_hist_raw[i]) (void)hipFree(e->d_hist_raw[i]);
@@ -1795,6 +1811,12 @@ int64_t process_dev(Engine* e, const void* d_in, int64_t count, void* d_out, voi
     const int64_t nout = out_size(e, count);
     int rc = 0;
     bool took_fft = false;
+    // The table's exceptions live for this call only: whatever way the call ends, the handle goes back to the rule chain alone,
+    // which is what configure() / upload_taps() / mf_plan() / chan_batch_wins() plan with.
+    struct AutoScope {
+        Engine* e;
+        ~AutoScope() { e->auto_pick = PICK_NONE; e->auto_veto = 0; e->auto_mode = 0; }
+    } auto_scope{e};
     e->auto_pick = PICK_NONE;
     e->auto_veto = 0;
     e->auto_mode = 0;
@@ -1841,7 +1863,7 @@ int64_t process_dev(Engine* e, const void* d_in, int64_t count, void* d_out, voi
         if (e->ch == 2) rc = e->rotate ? launch_win<2, true>(e, d_in, count, nout, d_out, s) : launch_win<2, false>(e, d_in, count, nout, d_out, s);
         else rc = launch_win<1, false>(e, d_in, count, nout, d_out, s);
         if (rc == 0) e->cur ^= 1;
-    } else if (use_core(e)) {
+    } else if (use_core(e) && e->taps_core) {      // (taps_core: d_taps has this kernel's layout -- a handle planned under QDSP_HIP_FORCE_ANY has not)
         qk::CoreArgs a;
         memset(&a, 0, sizeof(a));
         a.in = d_in;
@@ -1876,6 +1898,12 @@ int64_t process_dev(Engine* e, const void* d_in, int64_t count, void* d_out, voi
         a.hist = e->d_hist[e->cur];
         a.hist_next = e->d_hist[e->cur ^ 1];
         a.phases = e->d_taps;
+        if (e->taps_core) {
+            // QDSP_HIP_FORCE_ANY set after the plan was made: d_taps is branch-major, this kernel reads the phase table
+            rc = plain_taps(e);
+            if (rc) return rc;
+            a.phases = e->d_taps_plain;
+        }
         a.count = count;
         a.nout = nout;
         a.L = e->L;
