@@ -160,7 +160,7 @@ int chan_launch_uniform(Chan* c, const void* d_in, int64_t count, int64_t nout, 
     {   // second-order term of the per-output deviation rotation: only when 15 output times turn a channel by more than 1e-4 rad
         long long dmax = 0;
         for (int i = 0; i < 64; i++) dmax = std::max(dmax, a.ddelta[i] < 0 ? -a.ddelta[i] : a.ddelta[i]);
-        a.quad = 15.0 * (double)dmax * (double)a.M * 3.4061215800865545e-19 > 1e-4 || 0;
+        a.quad = 15.0 * (double)dmax * (double)a.M * 3.4061215800865545e-19 > 1e-4;
     }
     a.abl = qk::knob(qk::K_CHAN_ABL, 0);
     const size_t lds = qk::chan_uniform_lds_bytes(a.waves);
@@ -186,7 +186,7 @@ int chan_launch_batch_mf(Chan* c, const void* d_in, int64_t count, int64_t nout,
     // direct kernel (profiles/r02_tune_chan_batch.txt: even at 4 channels x 1e6 samples, 16 x 1e6: 36 against 55 us)
     if (count * c->nchan < (int64_t)qk::knob(qk::K_MF_BATCH_MIN_WORK, 1 << 22)) return 1;
     for (Engine* e : c->vfo)
-        if (e->cur != e0->cur || !e->rotate || e->ch != 2 || !e->d_taps_mf || e->mf_KJ != e0->mf_KJ || e->mf_QS != 1 || e->mf_keep2) return 1;
+        if (e->cur != e0->cur || !e->rotate || e->ch != 2 || !e->d_taps_mf || e->plan.mf.KJ != e0->plan.mf.KJ || e->plan.mf.QS != 1 || e->plan.mf.keep2) return 1;
     std::vector<qk::MfChanConst> key((size_t)c->nchan);
     for (int i = 0; i < c->nchan; i++) {
         Engine* e = c->vfo[i];
@@ -202,7 +202,7 @@ int chan_launch_batch_mf(Chan* c, const void* d_in, int64_t count, int64_t nout,
         dirty = key[i].hist[0] != c->batch_mf_key[i].hist[0] || key[i].hist[1] != c->batch_mf_key[i].hist[1] ||
                 key[i].dphase != c->batch_mf_key[i].dphase || key[i].gm1 != c->batch_mf_key[i].gm1;
     if (dirty) {
-        for (size_t i = 0; i < key.size(); i++) mf_rot_tables(key[i].dphase, e0->M, e0->mf_KJ, &key[i].rot_step, key[i].rot_k);
+        for (size_t i = 0; i < key.size(); i++) mf_rot_tables(key[i].dphase, e0->M, e0->plan.mf.KJ, &key[i].rot_step, key[i].rot_k);
         HIPCHK(hipDeviceSynchronize());     // (rare -- a retune: nothing in flight may still read the old table)
         if (c->d_batch_mf && c->batch_mf_key.size() != key.size()) { HIPCHK(hipFree(c->d_batch_mf)); c->d_batch_mf = nullptr; }
         if (!c->d_batch_mf) HIPCHK(hipMalloc(&c->d_batch_mf, key.size() * sizeof(qk::MfChanConst)));
@@ -221,7 +221,7 @@ int chan_launch_batch_mf(Chan* c, const void* d_in, int64_t count, int64_t nout,
     mf_tasks(a, nout, c->nchan, true);
     b.out_stride = out_stride;
     b.cur = e0->cur;
-    const int depth = qk::knob(qk::K_MF_DEPTH, e0->mf_KJ <= 8 ? 2 : 1);
+    const int depth = qk::knob(qk::K_MF_DEPTH, e0->plan.mf.KJ <= 8 ? 2 : 1);
     for (int base = 0; base < c->nchan; base += qk::kMfBatchMax) {
         const int nb = (c->nchan - base < qk::kMfBatchMax) ? c->nchan - base : qk::kMfBatchMax;
         b.tab = c->d_batch_mf + base;
@@ -231,7 +231,7 @@ int chan_launch_batch_mf(Chan* c, const void* d_in, int64_t count, int64_t nout,
             b.phase0[i] = c->vfo[base + i]->phase;
             b.outs[i] = out_ptrs ? out_ptrs[base + i] : nullptr;
         }
-        const int rc = qk::launch_mf_dec_batch(b, nb, e0->mf_KJ, depth, s);
+        const int rc = qk::launch_mf_dec_batch(b, nb, e0->plan.mf.KJ, depth, s);
         if (rc) return rc < 0 && rc != -1 ? rc : QDSP_HIP_EINVAL;
     }
     for (Engine* e : c->vfo) {
@@ -242,7 +242,7 @@ int chan_launch_batch_mf(Chan* c, const void* d_in, int64_t count, int64_t nout,
     c->last.name = "decim_mfma_batch_kernel";
     c->last.grid = ((a.ntasks + 3) / 4 + 1) * c->nchan;
     c->last.block = 256;
-    c->last.lds = 4 * (16 * (8 * e0->mf_KJ + 2) + 64) * (int)sizeof(float2);
+    c->last.lds = 4 * (16 * (8 * e0->plan.mf.KJ + 2) + 64) * (int)sizeof(float2);
     return 0;
 }
 
@@ -360,8 +360,7 @@ bool chan_batch_wins(const Chan* c, int64_t count) {
     const Engine* e = c->vfo[0];
     if (count <= (int64_t)(1 << 22)) return true;
     if (e->d_taps_mf && !qk::knob(qk::K_NO_MF, 0) && !qk::knob(qk::K_NO_MF_BATCH, 0)) return true;   // what each channel would run anyway
-    const bool dedicated = (fft_eligible(e, count) || use_win(e) || use_core(e) || use_lm(e));
-    return !dedicated;
+    return !has_dedicated_form(desc_of(e), count);
 }
 
 int64_t chan_process_dev(Chan* c, const void* d_in, int64_t count, void* d_out, int64_t out_stride, void* stream) {
@@ -483,7 +482,7 @@ int64_t qdsp_hip_chan_cf32_process_links(void* h, const void* in, int in_link, i
         if (!st) return QDSP_HIP_ENOMEM;
     }
     // host outputs are stored by the kernel itself into the pinned, device-mapped stream buffers (as process_ex does
-    // for results up to QDSP_HIP_DIRECT_OUT_MAX_BYTES); anything else is not served here -- the caller falls back
+    // for results up to 1 MiB); anything else is not served here -- the caller falls back
     std::vector<void*> dst((size_t)c->nchan);
     const size_t out_bytes = (size_t)nout * sizeof(float2);
     for (int i = 0; i < c->nchan; i++) {

@@ -1,6 +1,8 @@
 // engine.hip.h -- what the translation units of the host side share (round 3: qdsp_hip.hip, 3 159 lines, was split by operator):
-//   qdsp_hip.hip   the engine behind FIR / resampler / xlator / fused VFO (plans, tables, kernel selection: process_dev) and
-//                  their C entry points
+//   qdsp_hip.hip   the engine behind FIR / resampler / xlator / fused VFO (tap tables, launches; process_dev switches on the family
+//                  select() names) and their C entry points
+//   select.cpp     host only, plain C++ (select.h): which tables a handle gets (plan_of) and which kernel family serves a call
+//                  (select) -- pure functions of the handle's description, its plan, the call size and the switches (knobs.h)
 //   chan_ops.hip   the channelizer (Splitter -> N x VFO as one operator): uniform polyphase plan, batched per-channel kernels,
 //                  qdsp_hip_chan_cf32_*
 //   misc_ops.hip   element-wise math blocks (src/dsp/math.h), synthetic IQ, events, the timing / introspection helpers
@@ -18,6 +20,7 @@
 #include "rm_resamp.hip.h"
 #include "fir_lat.hip.h"
 #include "knobs.h"
+#include "select.h"
 #include "stream_op.h"
 #include <math.h>
 #include <stdio.h>
@@ -31,9 +34,6 @@
 
 namespace qh {
 
-constexpr int kMaxDynLds = 64 * 1024;  // default dynamic-LDS ceiling; tiles are sized under it
-
-enum Kind : int { KIND_FIR = 1, KIND_DECIM = 2, KIND_XLATE = 3, KIND_VFO = 4, KIND_CHAN = 5, KIND_SINE = 6 };
 constexpr uint32_t kMagic = 0x51445350u;  // "QDSP"
 
 // One engine serves FIR, resampler, xlator and the fused VFO: they differ only in
@@ -56,8 +56,8 @@ struct Engine {
     bool volk_gain = true;     // emulate the VOLK rotator's magnitude sawtooth (see rotate())
     float gm1 = 0.0f;          // |phase_inc| - 1
     // device state
-    float* d_taps = nullptr;       // core layout (branch-major, taps_core) or the phase table [L][P]
-    bool taps_core = false;        // the layout upload_taps() gave d_taps: the launch follows it, not QDSP_HIP_FORCE_ANY at call time
+    Plan plan;                     // what upload_taps() built (select.h): the launch follows it, not the switches at call time
+    float* d_taps = nullptr;       // core layout (branch-major, plan.core) or the phase table [L][P]
     float* d_taps_plain = nullptr; // the phase table beside a core-layout d_taps, built by the first call that needs it (plain_taps)
     double2* d_nco_tab = nullptr;  // tile_phasor tables of the direct kernels (fused NCO)
     unsigned long long nco_key_dphase = 0;
@@ -91,10 +91,6 @@ struct Engine {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // overlap-save fast convolution (FIR<complex_t> with many taps), fft_fir.hip.h
     int fir_mode = 0;           // 0 auto, 1 direct form, 2 overlap-save FFT
-    // (both hold only while process_dev runs: it clears them on every way out, so that plan-time code -- upload_taps, mf_plan, chan_batch_wins --
-    // sees the rule chain alone and a handle's tables do not depend on the calls it has served)
-    int auto_veto = 0, auto_mode = 0;   // integer decimators / fused VFO, AUTO: per-call exceptions to the rule chain named by the measured table (decim_table.inc)
-    int auto_pick = 0;          // FIR<complex_t>, AUTO: the kernel family the measured table names for this call (dispatch_table.inc), 0 = the rule chain
     float2* d_fft_H = nullptr;  // spectrum of the reversed taps / F, digit-reversed
     float2* d_fft_TA = nullptr;
     float2* d_fft_TB = nullptr;
@@ -113,11 +109,8 @@ struct Engine {
     long double rot_step_mult = 0.0L;
     double2 rot_step_val;
     unsigned long long fft_dphase = 0;   // NCO increment d_fft_H was built for (fused VFO), 0 otherwise
-    float* d_taps_rm = nullptr;    // rational MFMA resampler (rm_resamp.hip.h): A operands + first columns, built with the taps
-    int rm_ngrp = 0, rm_KB = 0, rm_ext = 0, rm_pitch = 0, rm_G = 0, rm_J = 1, rm_qpb = 1;
-    bool rm_big_only = false;     // plan admitted by the round-3 extension of the rule: chip-filling calls only (rm_min_count)
-    float* d_taps_mf = nullptr;    // MFMA decimator (mf_dec.hip.h): [2 KJ][64] A operands, built with the taps
-    int mf_KJ = 0, mf_QS = 1, mf_keep2 = 0;
+    float* d_taps_rm = nullptr;    // rational MFMA resampler (rm_resamp.hip.h): A operands + first columns, built with the taps (plan.rm)
+    float* d_taps_mf = nullptr;    // MFMA decimator (mf_dec.hip.h): [2 KJ][64] A operands, built with the taps (plan.mf)
     // polyphase overlap-save decimate-by-8 (pfb_dec.hip.h): column spectra + twiddles, built for (pfb_ntaps, pfb_dphase)
     float2* d_pfb = nullptr;
     int pfb_ntaps = -1;
@@ -133,7 +126,7 @@ struct Engine {
     Launch last;
 };
 
-struct AnyPlan { int Pp, tap_bytes; bool pad; long long tile, span; int ks_lanes, ks_shift, ks_chunk; };
+inline HandleDesc desc_of(const Engine* e) { return HandleDesc{e->kind, e->ch, e->rotate, e->has_filter, e->L, e->M, e->ntaps, e->P, e->fir_mode}; }
 
 constexpr uint32_t kChanMagic = 0x4348414eu;  // "CHAN"
 // the channelizer handle (chan_ops.hip; the harness helpers of misc_ops.hip take either kind of handle)
@@ -176,65 +169,24 @@ inline Chan* as_chan(void* h) {
 
 // ---- shared by the translation units (defined in qdsp_hip.hip; wait_stream, wait_event, shared_stream and mapped_host_ptr: stream_op.h) ----
 Engine* as_engine(void* h, Kind k);
-long double turns_of(float re, float im);
-unsigned long long fx_of_turns(long double t);
+Engine* any_engine(void* h);
 void unit_of_fx(unsigned long long ph, long double mult, double* c, double* s);
 void unit_of_fx_c(unsigned long long ph, long double mult, double* c, double* s);
 int64_t out_size(const Engine* e, int64_t count);
-int win_R(int M, int P);
-bool use_win(const Engine* e);
-bool use_lm(const Engine* e);
-bool mf_plan(const Engine* e, int* KJ, int* QS, int* keep2);
-int upload_taps(Engine* e, const float* taps, int ntaps);
-int configure(Engine* e, const float* taps, int ntaps, int interp, int decim);
 void set_inc_now(Engine* e, float re, float im);
 void set_inc(Engine* e, float re, float im);
 void apply_pending_inc(Engine* e);
-int ensure_io(Engine* e, int max_block);
 int create(void** h, Kind kind, int device, int ch, bool rotate, bool has_filter, int max_block);
 void destroy(Engine* e);
-int nco_tables(Engine* e, long long S, int NT, int na, const double2** tab);
-int launch_core_t(Engine* e, qk::CoreArgs& a, hipStream_t s);
-AnyPlan any_plan(int L, int M, int P, int ch, long long nout = -1);
 size_t fill_any_geometry(qk::AnyArgs& a, int ch, bool* lt, bool* pad, int nchan = 1);
-int fft_dec(const Engine* e);
-bool any_direct_wins(const Engine* e);
-bool fft_eligible(const Engine* e, int64_t count);
-void host_spectrum(const std::vector<long double>& gr, const std::vector<long double>& gi, int F, std::vector<double>& re, std::vector<double>& im);
-int fft_prepare(Engine* e);
-bool fft1k_eligible(const Engine* e, int64_t count);
-int fft1k_prepare(Engine* e);
-int launch_fft1k(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d_out, hipStream_t s);
-bool pfb_eligible(const Engine* e, int64_t count);
-int pfb_prepare(Engine* e);
-int raw_history(Engine* e, hipStream_t s, const float2** hist, float2** hist_raw_next);
-int launch_pfb(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d_out, hipStream_t s);
-int launch_fft(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d_out, hipStream_t s);
-int launch_xlate_raw(Engine* e, const void* d_in, int64_t count, void* d_out, unsigned long long phase0, float gm1, hipStream_t s);
-int launch_xlate(Engine* e, const void* d_in, int64_t count, void* d_out, hipStream_t s);
 void mf_tasks(qk::MfArgs& a, int64_t nout, int nchan, bool rot, bool real = false);
 void mf_rot_tables(unsigned long long dphase, int M, int KJ, double2* step, float2* rot_k);
-bool fir_lat_eligible(const Engine* e, int64_t count);
-int launch_fir_lat(Engine* e, const void* d_in, int64_t count, void* d_out, hipStream_t s);
-int launch_rm(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d_out, hipStream_t s);
-int launch_mf(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d_out, hipStream_t s);
-bool lm_yields_to_any(const Engine* e, int64_t nout);
-bool win_yields_to_fft1k(const Engine* e, int64_t count);
-int64_t mf_min_count(const Engine* e);
-int64_t rm_min_count(const Engine* e);
 int64_t process_dev(Engine* e, const void* d_in, int64_t count, void* d_out, void* stream);
-int64_t process_host(Engine* e, const float* in, int count, float* out);
-int64_t process_ex(Engine* e, const void* in, int in_dev, int count, void* out, int out_dev);
 int reset(Engine* e);
-int get_history(Engine* e, float* hist);
-int set_history(Engine* e, const float* hist);
 int set_history_dev(Engine* e, const void* d_hist, void* stream);
 int get_phase(Engine* e, float* re, float* im);
 int set_phase(Engine* e, float re, float im);
 int time_process(Engine* e, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
-Engine* any_engine(void* h);
-
-bool use_core(const Engine* e);
 
 // staging-side NCO constants of the direct-form kernels (used by qdsp_hip.hip and chan_ops.hip)
 template <class ARGS> void fill_stage_rot(ARGS& a, int NT) {
@@ -245,22 +197,6 @@ template <class ARGS> void fill_stage_rot(ARGS& a, int NT) {
         unit_of_fx_c(a.dphase, (long double)(k * NT), &c, &sn);
         a.rot_k[k] = make_float2((float)c, (float)sn);
     }
-}
-
-// tile_phasor's tables (kernels.hip.h), cached per handle for (dphase, S, NT, na); rebuilt on a retune or a new geometry
-
-template <class ARGS> int fill_stage_rot(Engine* e, ARGS& a, int NT, long long S, long long first, long long ntiles) {
-    fill_stage_rot(a, NT);
-    a.nco_tab = nullptr;
-    if (!e->rotate || 0) return 0;
-    const int na = (int)((ntiles + 255) / 256) + 1;
-    if (na > 65536) return 0;
-    int rc = nco_tables(e, S, NT, na, &a.nco_tab);
-    if (rc) return rc;
-    a.nco_na = e->nco_key_na;
-    const unsigned long long ph = a.phase0 + (unsigned long long)first * a.dphase;
-    unit_of_fx(ph, 1.0L, &a.nco_e0.x, &a.nco_e0.y);
-    return 0;
 }
 
 }  // namespace qh

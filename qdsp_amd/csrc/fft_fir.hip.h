@@ -15,10 +15,10 @@
 // Per-lane constants (pass twiddles, Hf slice) are loaded once per workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kconst.h"      // kFftN
 
 namespace qk {
 
-constexpr int kFftN = 4096;
 constexpr int kFftNT = 256;
 constexpr int kFftRow1 = 272;   // layout 1: [k0][n1*16 + n0], row padded 256 -> 272 elements
 constexpr int kFftRow2 = 17;    // layout 2: [k0*16 + k1][n0], row padded 16 -> 17 elements

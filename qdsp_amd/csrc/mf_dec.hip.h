@@ -28,11 +28,9 @@
 // by M / 2 with the same taps -- storing every other output (keep2).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kconst.h"      // kMfMaxKJ, kMfMaxQ
 
 namespace qk {
-
-constexpr int kMfMaxKJ = 16;      // K / 8: decimations up to 128
-constexpr int kMfMaxQ = 32;       // taps per column: two sets of 16 rows of the A operand
 
 struct MfArgs {
     const float2* in;

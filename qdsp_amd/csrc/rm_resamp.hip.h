@@ -27,12 +27,9 @@
 // output (48 kHz -> 44.1 kHz: 0.36 ms per 2^26 input samples, LDS-bound).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "kconst.h"      // kRmNE, kRmMaxGrp, kRmMaxKB, rm_lds_bytes
 
 namespace qk {
-
-constexpr int kRmNE = 12;         // samples per lane and tile held in registers: 4 G M + ext <= 768
-constexpr int kRmMaxGrp = 3;      // groups of 16 blocks = 64 outputs per period: L <= 192
-constexpr int kRmMaxKB = 40;      // band columns per block
 
 struct RmArgs {
     const float2* in;
@@ -57,10 +54,6 @@ struct RmArgs {
     float2 rot_k[kRmNE];          // exp(j 2pi 64 e dphase)
     float gm1;
 };
-
-inline size_t rm_lds_bytes(int ngrp, int KB, int G, int pitch, bool real = false) {
-    return (size_t)((ngrp * KB * 64 + 2 * ngrp * 64 + 3) & ~3) * 4 + 4 * ((size_t)4 * G * pitch + 64) * (real ? 4 : 8);      // A operands + block tables + four waves' tiles
-}
 
 int launch_rm_resamp(const RmArgs& a, bool rot, bool real, hipStream_t stream);      // real: float samples (in / out / hist reinterpreted), never with rot
 

@@ -11,7 +11,7 @@ namespace qh {
 
 // End-of-call wait of the host-pointer paths.  hipStreamSynchronize sleeps on an interrupt (~20 us to wake up),
 // longer than the kernels of a reference-sized block take: poll the stream for a bounded time first
-// (QDSP_HIP_SYNC_SPIN_US, default 200; 0 = always block).
+// (200 us).
 hipError_t wait_stream(hipStream_t s) {
     static const int spin_us = 200;
     if (spin_us > 0) {

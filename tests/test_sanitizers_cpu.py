@@ -9,6 +9,8 @@ the test pool and not wanted).
   -fsanitize=address,undefined;
 * qdsp_amd/csrc/stream_op.cpp: the host path the per-row operators share (link codes, staging, error precedence, creation and
   release) with a dummy operator on the same fake runtime, under -fsanitize=address,undefined.
+* qdsp_amd/csrc/select.cpp: filter planning and kernel selection, recomputing every line of the recorded dispatch map
+  (tests/golden/dispatch_map.txt) under -fsanitize=address,undefined -- any change of dispatch shows as a diff of that file.
 Pass = every program exits 0 and no sanitizer report appears on stderr."""
 import os
 import shutil
@@ -137,3 +139,16 @@ def test_stream_op_host_path_under_asan_ubsan():
     cxx(flags + ["-Wall", "-D__HIP_PLATFORM_AMD__", f"-I{hip_inc}", "-o", os.path.join(out, "stream_op_selftest"), "stream_op_selftest.cpp",
                  os.path.join(ROOT, "qdsp_amd", "csrc", "stream_op.cpp"), f"-L{out}", "-lfakehip", "-Wl,-rpath,$ORIGIN"])
     assert "stream_op ok" in run_clean([os.path.join(out, "stream_op_selftest")], cwd=out)
+
+
+def test_selector_recomputes_the_dispatch_map_under_asan_ubsan():
+    """qdsp_amd/csrc/select.cpp + knobs.cpp, plain C++: plan_of() and select() for every line of tests/golden/dispatch_map.txt -- the
+    kernel family of every call size of every row, under the default switches and the ones test_gpu_parity runs with -- must give the
+    map that scripts/dispatch_map.py recorded from the library's own calls; the map must reach every family and every setting of the
+    decimators' table.  (`select_selftest MAP --write` prints the selector's map, for a change that retunes on purpose.)"""
+    out = os.path.join(FAKE, "build", "address_select")
+    os.makedirs(out, exist_ok=True)
+    csrc = os.path.join(ROOT, "qdsp_amd", "csrc")
+    cxx(BASE + ["-fsanitize=address,undefined", "-Wall", "-o", os.path.join(out, "select_selftest"), "select_selftest.cpp",
+                os.path.join(csrc, "select.cpp"), os.path.join(csrc, "knobs.cpp")])
+    assert "select ok" in run_clean([os.path.join(out, "select_selftest"), os.path.join(HERE, "golden", "dispatch_map.txt")], cwd=out)
