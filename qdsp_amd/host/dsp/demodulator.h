@@ -2,7 +2,8 @@
 //
 // Drop-in for the data-parallel blocks of src/dsp/demodulator.h (:33-187, :332-497): same constructors, init(), setInput(),
 // setters / getters and public `out`.  run() is one call into libqdsp_hip between `_in->read()` and `out.swap()`, with the
-// same device links as FrequencyXlator (processing.h): a HIP-backed producer hands its block over in device memory.
+// device links of detail::hip_block (hip_block.h), the base of every block here: a HIP-backed producer hands its block over in
+// device memory.
 //   FloatFMDemod / FMDemod  qdsp_hip_demod_* (FM / FM_STEREO): bit-identical to the reference loop; the carried phase lives
 //                           on the device.  phasorSpeed is computed by the library from (sampleRate, deviation) exactly as
 //                           init() computes it.
@@ -20,72 +21,8 @@
 namespace dsp {
 
 namespace detail {
-// complex_t in, OUT out (float or stereo_t), one library handle; the derived block supplies the handle
-template <class OUT>
-class demod_base : public generic_block<demod_base<OUT>> {
-protected:
-    using base = generic_block<demod_base<OUT>>;
-    using process_fn = int (*)(void*, const void*, int, int, void*, int);
-    using destroy_fn = void (*)(void*);
-
-    demod_base(process_fn p, destroy_fn d, const char* who) : processEx(p), destroyFn(d), who(who) {}
-
-    ~demod_base() {
-        const bool live = base::running;
-        base::stop();
-        if (live && _in) { _in->releaseConsumer(); }
-        if (handle) { destroyFn(handle); }
-    }
-
-    // rc: what creating `handle` returned
-    void attach(stream<complex_t>* in, int rc) {
-        if (rc != 0) { handle = nullptr; hipBlockFail(who, rc); }
-        _in = in;
-        base::registerInput(_in);
-        base::registerOutput(&out);
-        _in->claimConsumer(handle != nullptr, true);
-    }
-
-public:
-    void setInput(stream<complex_t>* in) {
-        std::lock_guard<std::mutex> lck(base::ctrlMtx);
-        base::tempStop();
-        base::unregisterInput(_in);
-        _in->releaseConsumer();
-        _in = in;
-        _in->claimConsumer(handle != nullptr, true);
-        base::registerInput(_in);
-        base::tempStart();
-    }
-
-    int run() override {
-        const int count = _in->read();
-        if (count < 0) { return -1; }
-        if (!handle) { return -1; }
-        const bool inDev = _in->readOnDevice;
-        const bool outDev = out.consumerTakesDevice && out.ensureDevice(hipDeviceForBlocks());
-        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
-        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
-        void* evt = nullptr;
-        const int outLink = outDev ? out.linkOut(true) : done.arm(handle, evt);
-        const int rc = processEx(handle, src, _in->linkIn(), count, dst, outLink);
-        _in->flush();
-        if (rc != 0) { return hipBlockFail(who, rc); }
-        out.markWritten(outLink, evt);
-        if (!out.swap(count)) { return -1; }
-        return count;
-    }
-
-    stream<OUT> out;
-
-protected:
-    process_fn processEx;
-    destroy_fn destroyFn;
-    const char* who;
-    stream<complex_t>* _in = nullptr;
-    void* handle = nullptr;
-    done_events done;
-};
+// complex_t in, OUT out (float or stereo_t); a failing run() is reported under the bare class name
+template <class OUT> using demod_base = hip_block<complex_t, OUT>;
 
 // FloatFMDemod and FMDemod differ only in the output type (FMDemod: l == r, demodulator.h:169-170)
 template <class OUT>
@@ -104,22 +41,10 @@ public:
         db::attach(in, rc);
     }
 
-    void setSampleRate(float sampleRate) {
-        std::lock_guard<std::mutex> lck(db::base::ctrlMtx);
-        db::base::tempStop();
-        _sampleRate = sampleRate;
-        push();
-        db::base::tempStart();
-    }
+    void setSampleRate(float sampleRate) { db::paused([&] { _sampleRate = sampleRate; push(); }); }
     float getSampleRate() { return _sampleRate; }
 
-    void setDeviation(float deviation) {
-        std::lock_guard<std::mutex> lck(db::base::ctrlMtx);
-        db::base::tempStop();
-        _deviation = deviation;
-        push();
-        db::base::tempStart();
-    }
+    void setDeviation(float deviation) { db::paused([&] { _deviation = deviation; push(); }); }
     float getDeviation() { return _deviation; }
 
 private:

@@ -5,7 +5,8 @@
 // on the int-cast rates (resampling.h:28-30), taps designed by the window with gain
 // `interp` (resampling.h:34), phase split and per-block phase restart inside the library
 // (qdsp_hip_decim_*).  T = complex_t, stereo_t (same kernels: a float pair with real taps)
-// or float.
+// or float.  setInput(), run(), the public `stream<T> out` and the destructor are those of
+// detail::hip_block (hip_block.h).
 #pragma once
 #include <numeric>
 #include <type_traits>
@@ -18,105 +19,61 @@
 namespace dsp {
 
 template <class T>
-class PolyphaseResampler : public generic_block<PolyphaseResampler<T>> {
-    using base = generic_block<PolyphaseResampler<T>>;
+class PolyphaseResampler : public detail::hip_block<T, T> {
+    using hb = detail::hip_block<T, T>;
     static constexpr bool kPair = std::is_same<T, complex_t>::value || std::is_same<T, stereo_t>::value;
     static_assert(kPair || std::is_same<T, float>::value, "PolyphaseResampler<T>: T is complex_t, stereo_t or float");
 
 public:
-    PolyphaseResampler() {}
-    PolyphaseResampler(stream<T>* in, dsp::filter_window::generic_window* window, float inSampleRate, float outSampleRate) {
+    // (process_ex returns the output count; run() publishes that many and returns the input count)
+    PolyphaseResampler() : hb(kPair ? qdsp_hip_decim_cf32_process_ex : qdsp_hip_decim_f32_process_ex,
+                              kPair ? qdsp_hip_decim_cf32_destroy : qdsp_hip_decim_f32_destroy, "PolyphaseResampler::run", true) {}
+    PolyphaseResampler(stream<T>* in, dsp::filter_window::generic_window* window, float inSampleRate, float outSampleRate) : PolyphaseResampler() {
         init(in, window, inSampleRate, outSampleRate);
     }
 
-    ~PolyphaseResampler() {
-        const bool live = base::running;
-        base::stop();
-        if (live && _in) { _in->releaseConsumer(); }
-        if (handle) { kPair ? qdsp_hip_decim_cf32_destroy(handle) : qdsp_hip_decim_f32_destroy(handle); }
-    }
-
     void init(stream<T>* in, dsp::filter_window::generic_window* window, float inSampleRate, float outSampleRate) {
-        _in = in;
         _window = window;
         _inSampleRate = inSampleRate;
         _outSampleRate = outSampleRate;
         updateRatio();
         designTaps();
         const int dev = detail::hipDeviceForBlocks();
-        const int rc = kPair ? qdsp_hip_decim_cf32_create(&handle, dev, taps.data(), (int)taps.size(), _interp, _decim, STREAM_BUFFER_SIZE)
-                             : qdsp_hip_decim_f32_create(&handle, dev, taps.data(), (int)taps.size(), _interp, _decim, STREAM_BUFFER_SIZE);
-        if (rc != 0) { handle = nullptr; detail::hipBlockFail("PolyphaseResampler::init", rc); }
-        base::registerInput(_in);
-        base::registerOutput(&out);
-        _in->claimConsumer(handle != nullptr, true);
-    }
-
-    void setInput(stream<T>* in) {
-        std::lock_guard<std::mutex> lck(base::ctrlMtx);
-        base::tempStop();
-        base::unregisterInput(_in);
-        _in->releaseConsumer();
-        _in = in;
-        _in->claimConsumer(handle != nullptr, true);
-        base::registerInput(_in);
-        base::tempStart();
+        const int rc = kPair ? qdsp_hip_decim_cf32_create(&this->handle, dev, taps.data(), (int)taps.size(), _interp, _decim, STREAM_BUFFER_SIZE)
+                             : qdsp_hip_decim_f32_create(&this->handle, dev, taps.data(), (int)taps.size(), _interp, _decim, STREAM_BUFFER_SIZE);
+        hb::attach(in, rc, "PolyphaseResampler::init");
     }
 
     // The reference re-splits the EXISTING taps for the new ratio without redesigning them
     // (resampling.h:53-73); so does this.
     void setInSampleRate(float inSampleRate) {
-        std::lock_guard<std::mutex> lck(base::ctrlMtx);
-        base::tempStop();
-        _inSampleRate = inSampleRate;
-        updateRatio();
-        reconfigure();
-        base::tempStart();
+        hb::paused([&] {
+            _inSampleRate = inSampleRate;
+            updateRatio();
+            reconfigure();
+        });
     }
 
     void setOutSampleRate(float outSampleRate) {
-        std::lock_guard<std::mutex> lck(base::ctrlMtx);
-        base::tempStop();
-        _outSampleRate = outSampleRate;
-        updateRatio();
-        reconfigure();
-        base::tempStart();
+        hb::paused([&] {
+            _outSampleRate = outSampleRate;
+            updateRatio();
+            reconfigure();
+        });
     }
 
     int getInterpolation() { return _interp; }
     int getDecimation() { return _decim; }
 
     void updateWindow(dsp::filter_window::generic_window* window) {
-        std::lock_guard<std::mutex> lck(base::ctrlMtx);
-        base::tempStop();
-        _window = window;
-        designTaps();
-        reconfigure();
-        base::tempStart();
+        hb::paused([&] {
+            _window = window;
+            designTaps();
+            reconfigure();
+        });
     }
 
     int calcOutSize(int in) override { return (in * _interp) / _decim; }
-
-    int run() override {
-        const int count = _in->read();
-        if (count < 0) { return -1; }
-        if (!handle) { return -1; }
-        const bool inDev = _in->readOnDevice;
-        const bool outDev = out.consumerTakesDevice && out.ensureDevice(detail::hipDeviceForBlocks());
-        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
-        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
-        void* evt = nullptr;
-        const int inLink = _in->linkIn(), outLink = outDev ? out.linkOut(true) : done.arm(handle, evt);
-        const int outCount = kPair ? qdsp_hip_decim_cf32_process_ex(handle, src, inLink, count, dst, outLink)
-                                   : qdsp_hip_decim_f32_process_ex(handle, src, inLink, count, dst, outLink);
-        _in->flush();
-        if (outCount < 0) { return detail::hipBlockFail("PolyphaseResampler::run", outCount); }
-        out.markWritten(outLink, evt);
-        if (!out.swap(outCount)) { return -1; }
-        return count;
-    }
-
-    stream<T> out;
 
 private:
     void updateRatio() {
@@ -133,19 +90,16 @@ private:
     }
 
     void reconfigure() {
-        if (!handle) { return; }
-        const int rc = kPair ? qdsp_hip_decim_cf32_configure(handle, taps.data(), (int)taps.size(), _interp, _decim)
-                             : qdsp_hip_decim_f32_configure(handle, taps.data(), (int)taps.size(), _interp, _decim);
+        if (!this->handle) { return; }
+        const int rc = kPair ? qdsp_hip_decim_cf32_configure(this->handle, taps.data(), (int)taps.size(), _interp, _decim)
+                             : qdsp_hip_decim_f32_configure(this->handle, taps.data(), (int)taps.size(), _interp, _decim);
         if (rc != 0) { detail::hipBlockFail("PolyphaseResampler::reconfigure", rc); }
     }
 
-    stream<T>* _in = nullptr;
     dsp::filter_window::generic_window* _window = nullptr;
     int _interp = 1, _decim = 1;
     float _inSampleRate = 1.0f, _outSampleRate = 1.0f;
     std::vector<float> taps;
-    void* handle = nullptr;
-    detail::done_events done;
 };
 
 }  // namespace dsp

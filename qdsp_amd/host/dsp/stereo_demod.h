@@ -36,30 +36,26 @@ public:
     }
 
     void setSampleRate(float sampleRate) {
-        std::lock_guard<std::mutex> lck(db::base::ctrlMtx);
-        db::base::tempStop();
-        _sampleRate = sampleRate;
-        win.setSampleRate(_sampleRate);
-        makeTaps();
-        if (handle) {
+        paused([&] {
+            _sampleRate = sampleRate;
+            win.setSampleRate(_sampleRate);
+            makeTaps();
+            if (!handle) { return; }
             int rc = qdsp_hip_stereo_fm_set_fm(handle, 0, _sampleRate, _deviation);
             if (rc == 0) { rc = qdsp_hip_stereo_fm_set_pilot_taps(handle, taps.data(), (int)taps.size()); }
             if (rc != 0) { detail::hipBlockFail("StereoFMDemod::setSampleRate", rc); }
-        }
-        db::base::tempStart();
+        });
     }
 
     float getSampleRate() { return _sampleRate; }
 
     void setDeviation(float deviation) {
-        std::lock_guard<std::mutex> lck(db::base::ctrlMtx);
-        db::base::tempStop();
-        _deviation = deviation;
-        if (handle) {
+        paused([&] {
+            _deviation = deviation;
+            if (!handle) { return; }
             const int rc = qdsp_hip_stereo_fm_set_fm(handle, 0, _sampleRate, _deviation);
             if (rc != 0) { detail::hipBlockFail("StereoFMDemod::setDeviation", rc); }
-        }
-        db::base::tempStart();
+        });
     }
 
     float getDeviation() { return _deviation; }

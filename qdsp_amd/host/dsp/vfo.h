@@ -25,14 +25,15 @@ namespace dsp {
 
 namespace detail {
 // The fused worker: reads IQ, writes translated + resampled IQ.
-class XlatingResampler : public generic_block<XlatingResampler> {
-    using base = generic_block<XlatingResampler>;
+class XlatingResampler : public hip_block<complex_t, complex_t> {
+    using hb = hip_block<complex_t, complex_t>;
+    using hb::setInput;     // (the VFO has no input setter, and a rebound core would leave its bank member on the old stream)
 
 public:
-    XlatingResampler() {}
+    // (process_ex returns the output count; run() publishes that many and returns the input count)
+    XlatingResampler() : hb(qdsp_hip_xlate_fir_decim_cf32_process_ex, qdsp_hip_xlate_fir_decim_cf32_destroy, "VFO::run", true) {}
     ~XlatingResampler() {
-        const bool live = base::running;
-        base::stop();
+        halt();     // first: the worker reads `member`, and what follows is shared with a Splitter's worker
         {
             // under designMtx: the Splitter's dropBank / buildBank test `alive` and use `handle` / `out` under the same mutex, so they
             // never hand a destroyed engine to qdsp_hip_chan_cf32_move_channel_state
@@ -42,15 +43,12 @@ public:
             member->out = nullptr;
         }
         if (auto ctl = std::atomic_load(&member->ctl)) { ctl->broken.store(true); }
-        if (live && _in) { _in->releaseConsumer(); }
-        if (handle) { qdsp_hip_xlate_fir_decim_cf32_destroy(handle); }
-    }
+    }   // (~hip_block destroys the handle)
 
     void init(stream<complex_t>* in, const std::vector<float>& taps, int interp, int decim, float dRe, float dIm) {
-        _in = in;
         const int rc = qdsp_hip_xlate_fir_decim_cf32_create(&handle, hipDeviceForBlocks(), taps.data(), (int)taps.size(), interp,
                                                             decim, dRe, dIm, STREAM_BUFFER_SIZE);
-        if (rc != 0) { handle = nullptr; hipBlockFail("VFO::init", rc); }
+        if (rc != 0) { handle = nullptr; }
         {
             std::lock_guard<std::mutex> lk(member->designMtx);
             member->taps = taps;
@@ -61,27 +59,23 @@ public:
             member->out = &out;
             member->handle = handle;
         }
-        if (handle) { _in->bankMember = member; }     // (a Splitter upstream may run identical VFOs as one batched launch: vfo_bank.h)
-        base::registerInput(_in);
-        base::registerOutput(&out);
-        _in->claimConsumer(handle != nullptr, true);
+        if (handle) { in->bankMember = member; }     // (a Splitter upstream may run identical VFOs as one batched launch: vfo_bank.h)
+        hb::attach(in, rc, "VFO::init");
     }
 
     void configure(const std::vector<float>& taps, int interp, int decim) {
-        std::lock_guard<std::mutex> lck(base::ctrlMtx);
-        base::tempStop();
-        {
-            std::lock_guard<std::mutex> lk(member->designMtx);
-            member->taps = taps;
-            member->interp = interp;
-            member->decim = decim;
-        }
-        if (auto ctl = std::atomic_load(&member->ctl)) { ctl->broken.store(true); }   // a bank built for the old design is taken down by its Splitter
-        if (handle) {
+        paused([&] {
+            {
+                std::lock_guard<std::mutex> lk(member->designMtx);
+                member->taps = taps;
+                member->interp = interp;
+                member->decim = decim;
+            }
+            if (auto ctl = std::atomic_load(&member->ctl)) { ctl->broken.store(true); }   // a bank built for the old design is taken down by its Splitter
+            if (!handle) { return; }
             const int rc = qdsp_hip_xlate_fir_decim_cf32_configure(handle, taps.data(), (int)taps.size(), interp, decim);
             if (rc != 0) { hipBlockFail("VFO::configure", rc); }
-        }
-        base::tempStart();
+        });
     }
 
     void setPhaseInc(float dRe, float dIm) {
@@ -98,9 +92,8 @@ public:
     }
 
     int run() override {
-        const int count = _in->read();
+        const int count = take();
         if (count < 0) { return -1; }
-        if (!handle) { return -1; }
         if (_in->readIsToken) {
             // banked (Splitter -> N x identical VFO): the block is a token, the Splitter's batched launch has already put
             // this channel's samples into out's write buffer.  Flush AFTER the swap: the Splitter takes the flush as
@@ -113,27 +106,10 @@ public:
             _in->flush();
             return ok ? count : -1;
         }
-        const bool inDev = _in->readOnDevice;
-        const bool outDev = out.consumerTakesDevice && out.ensureDevice(hipDeviceForBlocks());
-        const void* src = inDev ? static_cast<const void*>(_in->devReadBuf) : static_cast<const void*>(_in->readBuf);
-        void* dst = outDev ? static_cast<void*>(out.devWriteBuf) : static_cast<void*>(out.writeBuf);
-        void* evt = nullptr;
-        const int outLink = outDev ? out.linkOut(true) : done.arm(handle, evt);
-        const int outCount = qdsp_hip_xlate_fir_decim_cf32_process_ex(handle, src, _in->linkIn(), count, dst, outLink);
-        _in->flush();
-        if (outCount < 0) { return hipBlockFail("VFO::run", outCount); }
-        out.markWritten(outLink, evt);
-        if (!out.swap(outCount)) { return -1; }
-        return count;
+        return finish(count);
     }
 
-    stream<complex_t> out;
     std::shared_ptr<vfo_bank_member> member = std::make_shared<vfo_bank_member>();
-
-private:
-    stream<complex_t>* _in = nullptr;
-    void* handle = nullptr;
-    detail::done_events done;
 };
 }  // namespace detail
 

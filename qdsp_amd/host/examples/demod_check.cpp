@@ -28,6 +28,12 @@
 //   demod_check sfm <in.cf32> <out> <block> <sampleRate> <deviation>
 //                   source -> StereoFMDemod (dsp/stereo_demod.h) -> sink: the file is the demodulator's own input, read in blocks of
 //                   <block> samples, one run() each; stereo_t out.
+//   demod_check rebind <block> <before> <after>
+//                   two sources of constant blocks, A = 1+0j and B = 2+0j; A -> Squelch (open) -> sink, and after <before> blocks
+//                   have come out setInput() moves the running Squelch to B, until <after> blocks of B have come out.  Every
+//                   block must be all A or all B, and no A may follow a B.  (How many blocks are lost across the switch is not
+//                   fixed: the worker may be stopped with a block in hand.)
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -112,13 +118,14 @@ static int runGraph(const char* inPath, const char* outPath, int block, float of
         if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) { fprintf(stderr, "graph timed out\n"); return 3; }
         if (hipBlockErrors() > 0) { fprintf(stderr, "a block failed\n"); return 4; }
     }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     src.stop();
     vfo.stop();
     for (auto* b : blks) { b->stop(); }
     sink.stop();
     for (auto it = blks.rbegin(); it != blks.rend(); ++it) { delete *it; }
     w.file.close();
-    printf("graph ok: %zu in, %ld out, %ld blocks, %s link\n", feed.data.size(), w.samples.load(), nblocks, hostLink ? "host" : "device");
+    printf("graph ok: %zu in, %ld out, %ld blocks, %s link, %.1f ms\n", feed.data.size(), w.samples.load(), nblocks, hostLink ? "host" : "device", ms);
     return 0;
 }
 
@@ -150,12 +157,82 @@ static int runStereo(const char* inPath, const char* outPath, int block, float s
     return 0;
 }
 
+// a source of blocks of one constant, and a sink that sorts the blocks it gets by that constant
+struct Constant {
+    complex_t value;
+    int block;
+    static int pull(complex_t* dst, void* ctx) {
+        const Constant* c = static_cast<const Constant*>(ctx);
+        std::fill(dst, dst + c->block, c->value);
+        return c->block;
+    }
+};
+
+struct Sorter {
+    std::atomic<long> a{0}, b{0}, mixed{0}, aAfterB{0}, other{0};
+    static void push(complex_t* src, int count, void* ctx) {
+        Sorter* s = static_cast<Sorter*>(ctx);
+        int na = 0, nb = 0;
+        for (int i = 0; i < count; i++) {
+            na += src[i].re == 1.0f && src[i].im == 0.0f;
+            nb += src[i].re == 2.0f && src[i].im == 0.0f;
+        }
+        if (na == count) { s->a++; if (s->b.load() > 0) { s->aAfterB++; } }
+        else if (nb == count) { s->b++; }
+        else if (na + nb == count) { s->mixed++; }
+        else { s->other++; }
+    }
+};
+
+static int runRebind(int block, long before, long after) {
+    if (block < 1 || block > STREAM_BUFFER_SIZE || before < 1 || after < 1) { fprintf(stderr, "rebind: <block> <before> <after>\n"); return 2; }
+    Constant ca{complex_t{1.0f, 0.0f}, block}, cb{complex_t{2.0f, 0.0f}, block};
+    HandlerSource<complex_t> srcA(Constant::pull, &ca), srcB(Constant::pull, &cb);
+    Squelch sq(&srcA.out, -100.0f);      // |x| = 1 is 0 dB: open
+    Sorter sorted;
+    HandlerSink<complex_t> sink(&sq.out, Sorter::push, &sorted);
+    sink.start();
+    sq.start();
+    srcA.start();
+    srcB.start();
+    const auto t0 = std::chrono::steady_clock::now();
+    auto waitFor = [&](std::atomic<long>& n, long want) {
+        while (n.load() < want) {
+            std::this_thread::sleep_for(std::chrono::milliseconds(1));
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) { fprintf(stderr, "graph timed out\n"); return 3; }
+            if (hipBlockErrors() > 0) { fprintf(stderr, "a block failed\n"); return 4; }
+        }
+        return 0;
+    };
+    int rc = waitFor(sorted.a, before);
+    if (rc == 0) {
+        sq.setInput(&srcB.out);
+        rc = waitFor(sorted.b, after);
+    }
+    srcA.stop();
+    srcB.stop();
+    sq.stop();
+    sink.stop();
+    if (rc != 0) { return rc; }
+    const long mixed = sorted.mixed.load(), late = sorted.aAfterB.load(), other = sorted.other.load();
+    if (mixed || late || other) {
+        fprintf(stderr, "rebind: %ld mixed blocks, %ld blocks of A after a block of B, %ld blocks of neither\n", mixed, late, other);
+        return 5;
+    }
+    printf("graph ok: %ld blocks of A, then %ld blocks of B\n", sorted.a.load(), sorted.b.load());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
     const std::string mode = argv[1];
     if (mode == "sfm") {
         if (argc < 7) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
         return runStereo(argv[2], argv[3], atoi(argv[4]), (float)atof(argv[5]), (float)atof(argv[6]));
+    }
+    if (mode == "rebind") {
+        if (argc < 5) { fprintf(stderr, "usage: see the header of demod_check.cpp\n"); return 2; }
+        return runRebind(atoi(argv[2]), atol(argv[3]), atol(argv[4]));
     }
     if (mode == "vfo" && argc >= 9) {
         const float off = (float)atof(argv[5]), inSR = (float)atof(argv[6]), outSR = (float)atof(argv[7]), bw = (float)atof(argv[8]);

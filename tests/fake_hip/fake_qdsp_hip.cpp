@@ -24,6 +24,9 @@ constexpr unsigned kMagic = 0x46414b45u;   // "FAKE"
 struct Op {
     unsigned magic = kMagic;
     int elem = 8;                // bytes per sample: 8 = float pair, 4 = float
+    int outElem = 8;             // ... of the output (the demodulators: complex in, float or stereo_t out)
+    int window = 1;              // FeedForwardAGC: window - 1 samples are held back
+    long long fill = 0;          // ... of which so many are held now
     int interp = 1, decim = 1;
     int nchan = 1;
     std::atomic<long long> calls{0};
@@ -39,7 +42,7 @@ int make(void** h, int elem, int interp, int decim, int nchan = 1) {
     if (!h || interp < 1 || decim < 1 || nchan < 1) return QDSP_HIP_EINVAL;
     Op* o = new (std::nothrow) Op;
     if (!o) return QDSP_HIP_ENOMEM;
-    o->elem = elem;
+    o->elem = o->outElem = elem;
     o->interp = interp;
     o->decim = decim;
     o->nchan = nchan;
@@ -80,6 +83,25 @@ long long resample_copy(Op* o, const void* in, long long count, void* out) {
     }
     o->calls++;
     return no;
+}
+
+// a per-row operator with its own output sample size: out[n] = the leading bytes of in[n]; 0 or an error, as *_process_ex
+int row_copy(void* h, const void* in, int count, void* out) {
+    Op* o = op(h);
+    if (!o) return QDSP_HIP_EINVAL;
+    if (o->outElem == o->elem) { const long long r = resample_copy(o, in, count, out); return r < 0 ? (int)r : 0; }
+    if (count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
+    jitter(o);
+    const int nb = o->outElem < o->elem ? o->outElem : o->elem;
+    for (long long n = 0; n < count; n++) memcpy(static_cast<char*>(out) + n * o->outElem, static_cast<const char*>(in) + n * o->elem, (size_t)nb);
+    o->calls++;
+    return 0;
+}
+
+int make_row(void** h, int inElem, int outElem, int nchan) {
+    const int rc = make(h, inElem, 1, 1, nchan);
+    if (rc == 0) static_cast<Op*>(*h)->outElem = outElem;
+    return rc;
 }
 
 }  // namespace
@@ -207,6 +229,84 @@ int qdsp_hip_math_process_ex(void* h, const void* a, int, const void* b, int, in
     return 0;
 }
 void qdsp_hip_math_destroy(void* h) { unmake(h); }
+
+// ---- the per-row operators behind dsp/demodulator.h, stereo_demod.h, deemp.h, pll.h and the level blocks of processing.h ----
+int qdsp_hip_demod_create(void** h, int, int kind, int nchan, int) {
+    if (kind != QDSP_HIP_DEMOD_FM && kind != QDSP_HIP_DEMOD_FM_STEREO && kind != QDSP_HIP_DEMOD_AM) return QDSP_HIP_EINVAL;
+    return make_row(h, 8, kind == QDSP_HIP_DEMOD_FM_STEREO ? 8 : 4, nchan);
+}
+int qdsp_hip_demod_set_fm(void* h, int, float, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_demod_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_demod_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_ssb_cf32_create(void** h, int, float, float, int) { return make_row(h, 8, 4, 1); }
+int qdsp_hip_ssb_cf32_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+int qdsp_hip_ssb_cf32_set_phase_inc(void* h, float, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+void qdsp_hip_ssb_cf32_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_stereo_fm_create(void** h, int, int nchan, const float* taps, int ntaps, int) { return (taps && ntaps > 0) ? make_row(h, 8, 8, nchan) : QDSP_HIP_EINVAL; }
+int qdsp_hip_stereo_fm_set_fm(void* h, int, float, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_stereo_fm_set_pilot_taps(void* h, const float* t, int n) { return (op(h) && t && n > 0) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_stereo_fm_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_stereo_fm_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_deemp_create(void** h, int, int kind, int nchan, int) {
+    if (kind != QDSP_HIP_DEEMP_MONO && kind != QDSP_HIP_DEEMP_STEREO) return QDSP_HIP_EINVAL;
+    return make_row(h, kind == QDSP_HIP_DEEMP_STEREO ? 8 : 4, kind == QDSP_HIP_DEEMP_STEREO ? 8 : 4, nchan);
+}
+int qdsp_hip_deemp_set(void* h, int, float, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_deemp_set_bypass(void* h, int) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_deemp_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_deemp_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_squelch_create(void** h, int, int nchan, int) { return make_row(h, 8, 8, nchan); }
+int qdsp_hip_squelch_set_level(void* h, int, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_squelch_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_squelch_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_agc_create(void** h, int, int nchan, int) { return make_row(h, 4, 4, nchan); }
+int qdsp_hip_agc_set(void* h, int, float, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_agc_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_agc_destroy(void* h) { unmake(h); }
+
+// FeedForwardAGC: window - 1 samples are held back, so a call emits what it is given less what the history still lacks
+int qdsp_hip_ffagc_create(void** h, int, int kind, int nchan, int, int window) {
+    if ((kind != QDSP_HIP_FFAGC_REAL && kind != QDSP_HIP_FFAGC_COMPLEX) || window < 1) return QDSP_HIP_EINVAL;
+    const int elem = kind == QDSP_HIP_FFAGC_COMPLEX ? 8 : 4;
+    const int rc = make_row(h, elem, elem, nchan);
+    if (rc == 0) static_cast<Op*>(*h)->window = window;
+    return rc;
+}
+int64_t qdsp_hip_ffagc_out_size(void* h, int64_t count) {
+    Op* o = op(h);
+    if (!o || count < 0) return QDSP_HIP_EINVAL;
+    const long long n = o->fill + count - (o->window - 1);
+    return n > 0 ? n : 0;
+}
+int qdsp_hip_ffagc_process_ex(void* h, const void* in, int, int count, void* out, int) {
+    Op* o = op(h);
+    if (!o || count < 0 || (count > 0 && (!in || !out))) return QDSP_HIP_EINVAL;
+    const long long n = qdsp_hip_ffagc_out_size(h, count);
+    jitter(o);
+    // the last n samples of the call (n <= count once the history is full; the first emitting call may reach into it: zeros)
+    const long long fromCall = n < count ? n : count;
+    if (n > fromCall) memset(out, 0, (size_t)(n - fromCall) * o->elem);
+    if (fromCall) memcpy(static_cast<char*>(out) + (n - fromCall) * o->elem, static_cast<const char*>(in) + (count - fromCall) * o->elem, (size_t)fromCall * o->elem);
+    o->fill = o->fill + count - n;
+    o->calls++;
+    return (int)n;
+}
+void qdsp_hip_ffagc_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_cagc_create(void** h, int, int nchan, int) { return make_row(h, 8, 8, nchan); }
+int qdsp_hip_cagc_set(void* h, int, float, float, float) { return op(h) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_cagc_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_cagc_destroy(void* h) { unmake(h); }
+
+int qdsp_hip_costas_create(void** h, int, int order, int nchan, int) { return (order == 2 || order == 4 || order == 8) ? make_row(h, 8, 8, nchan) : QDSP_HIP_EINVAL; }
+int qdsp_hip_costas_set_bandwidth(void* h, int, float bw) { return (op(h) && bw >= 0.0f) ? 0 : QDSP_HIP_EINVAL; }
+int qdsp_hip_costas_process_ex(void* h, const void* in, int, int count, void* out, int) { return row_copy(h, in, count, out); }
+void qdsp_hip_costas_destroy(void* h) { unmake(h); }
 
 // ---- ring: not available in the fake (graph_check `shard` is a GPU test) ----
 int qdsp_hip_ring_available(void) { return 0; }

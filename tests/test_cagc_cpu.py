@@ -258,7 +258,7 @@ _SURFACE_SRC = r"""
 #include "dsp/vfo.h"
 using namespace dsp;
 static_assert(std::is_same<decltype(ComplexAGC::out), stream<complex_t>>::value, "ComplexAGC::out");
-static_assert(std::is_base_of<generic_block<ComplexAGC>, ComplexAGC>::value, "generic_block<ComplexAGC>");
+static_assert(std::is_base_of<detail::hip_block<complex_t, complex_t>, ComplexAGC>::value, "the shared base of the HIP-backed blocks");
 void use(stream<complex_t>* in) {
     ComplexAGC a(in, 1.0f, 65535, 0.001f);
     a.setSetPoint(0.5f); a.setMaxGain(10.0f); a.setRate(0.01f); a.setInput(in);
@@ -276,7 +276,7 @@ def test_complex_agc_block_compiles_with_the_reference_usage(tmp_path):
     (tmp_path / "s.cpp").write_text(_SURFACE_SRC)
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Wno-unused-parameter", "-I", HOST,
                            "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.cpp")])
-    src = open(os.path.join(HOST, "dsp", "processing.h")).read()
+    src = open(os.path.join(HOST, "dsp", "processing.h")).read() + open(os.path.join(HOST, "dsp", "hip_block.h")).read()    # (the link protocol is the base's)
     for name in ("claimConsumer", "done.arm", "qdsp_hip_cagc_process_ex", "qdsp_hip_cagc_set"):
         assert name in src, name
 

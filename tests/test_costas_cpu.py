@@ -438,7 +438,7 @@ _SURFACE_SRC = r"""
 #include "dsp/pll.h"
 using namespace dsp;
 static_assert(std::is_same<decltype(CostasLoop<4>::out), stream<complex_t>>::value, "CostasLoop::out");
-static_assert(std::is_base_of<generic_block<CostasLoop<8>>, CostasLoop<8>>::value, "generic_block<CostasLoop<ORDER>>");
+static_assert(std::is_base_of<detail::hip_block<complex_t, complex_t>, CostasLoop<8>>::value, "the shared base of the HIP-backed blocks");
 template <int ORDER> struct Demod {           // demodulator.h:566-682, the members and calls that touch the loop
     void init(stream<complex_t>* input, float agcRate, float costasLoopBw) {
         agc.init(input, 1.0f, 65535, agcRate);
@@ -466,7 +466,7 @@ def test_costas_block_compiles_with_the_reference_usage(tmp_path):
     (tmp_path / "s.cpp").write_text(_SURFACE_SRC)
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Wno-unused-parameter", "-I", HOST,
                            "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.cpp")])
-    src = open(os.path.join(HOST, "dsp", "pll.h")).read()
+    src = open(os.path.join(HOST, "dsp", "pll.h")).read() + open(os.path.join(HOST, "dsp", "hip_block.h")).read()    # (the link protocol is the base's)
     for name in ("claimConsumer", "done.arm", "qdsp_hip_costas_process_ex", "qdsp_hip_costas_set_bandwidth"):
         assert name in src, name
 

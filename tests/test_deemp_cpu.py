@@ -160,7 +160,7 @@ _SURFACE_SRC = r"""
 using namespace dsp;
 static_assert(std::is_same<decltype(BFMDeemp::out), stream<stereo_t>>::value, "BFMDeemp::out");
 static_assert(std::is_same<decltype(BFMDeemp::bypass), bool>::value, "BFMDeemp::bypass");
-static_assert(std::is_base_of<generic_block<BFMDeemp>, BFMDeemp>::value, "generic_block<BFMDeemp>");
+static_assert(std::is_base_of<detail::hip_block<stereo_t, stereo_t>, BFMDeemp>::value, "the shared base of the HIP-backed blocks");
 void use(stream<complex_t>* iq, stream<stereo_t>* in) {
     BFMDeemp a(in, 48000.0f, 50e-6f);
     a.setSampleRate(44100.0f); a.setTau(75e-6f); a.setInput(in); a.bypass = true;
@@ -178,7 +178,7 @@ def test_bfmdeemp_block_compiles_with_the_reference_types(tmp_path):
     (tmp_path / "s.cpp").write_text(_SURFACE_SRC)
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Wno-unused-parameter", "-I", HOST,
                            "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.cpp")])
-    src = open(os.path.join(HOST, "dsp", "deemp.h")).read()
+    src = open(os.path.join(HOST, "dsp", "deemp.h")).read() + open(os.path.join(HOST, "dsp", "hip_block.h")).read()    # (the link protocol is the base's)
     for name in ("claimConsumer", "done.arm", "qdsp_hip_deemp_process_ex", "qdsp_hip_deemp_set_bypass"):
         assert name in src, name
     # graph_check is linked against the fake library of the sanitizer test, which has no de-emphasis symbols

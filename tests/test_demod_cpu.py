@@ -183,7 +183,7 @@ def test_demod_symbols_declared_and_exported():
 
 
 def test_demodulator_header_keeps_the_reference_surface():
-    src = open(os.path.join(HOST, "dsp", "demodulator.h")).read()
+    src = open(os.path.join(HOST, "dsp", "demodulator.h")).read() + open(os.path.join(HOST, "dsp", "hip_block.h")).read()    # (the link protocol is the base's)
     for cls in ("FloatFMDemod", "FMDemod", "AMDemod", "SSBDemod"):
         assert re.search(rf"class {cls}\b", src), cls
     for name in ("init", "setInput", "setSampleRate", "getSampleRate", "setDeviation", "getDeviation", "setBandWidth", "setMode", "run"):

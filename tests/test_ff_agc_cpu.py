@@ -258,8 +258,8 @@ _SURFACE_SRC = r"""
 using namespace dsp;
 static_assert(std::is_same<decltype(FeedForwardAGC<float>::out), stream<float>>::value, "FeedForwardAGC<float>::out");
 static_assert(std::is_same<decltype(FeedForwardAGC<complex_t>::out), stream<complex_t>>::value, "FeedForwardAGC<complex_t>::out");
-static_assert(std::is_base_of<generic_block<FeedForwardAGC<float>>, FeedForwardAGC<float>>::value, "generic_block");
-static_assert(std::is_base_of<generic_block<FeedForwardAGC<complex_t>>, FeedForwardAGC<complex_t>>::value, "generic_block");
+static_assert(std::is_base_of<detail::hip_block<float, float>, FeedForwardAGC<float>>::value, "the shared base of the HIP-backed blocks");
+static_assert(std::is_base_of<detail::hip_block<complex_t, complex_t>, FeedForwardAGC<complex_t>>::value, "the shared base of the HIP-backed blocks");
 static_assert(std::is_default_constructible<FeedForwardAGC<float>>::value, "FeedForwardAGC()");
 static_assert(std::is_constructible<FeedForwardAGC<complex_t>, stream<complex_t>*>::value, "FeedForwardAGC(stream<T>*)");
 static_assert(std::is_same<decltype(std::declval<FeedForwardAGC<float>&>().run()), int>::value, "int run()");
@@ -281,7 +281,7 @@ def test_feed_forward_agc_block_compiles_with_the_reference_surface(tmp_path):
     (tmp_path / "s.cpp").write_text(_SURFACE_SRC)
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Wno-unused-parameter", "-I", HOST,
                            "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.cpp")])
-    src = open(os.path.join(HOST, "dsp", "processing.h")).read()
+    src = open(os.path.join(HOST, "dsp", "processing.h")).read() + open(os.path.join(HOST, "dsp", "hip_block.h")).read()    # (the link protocol is the base's)
     body = src[src.index("class FeedForwardAGC"):]
     for name in ("claimConsumer", "done.arm", "qdsp_hip_ffagc_process_ex", "qdsp_hip_ffagc_out_size", "linkIn()", "sampleCount = 1024"):
         assert name in body, name

@@ -72,3 +72,11 @@ def test_ssb_block(graph, link, mode):
     vb = BLOCK // DECIM
     want = np.concatenate([xl.process(v[a:a + vb]).real for a in range(0, len(v), vb)])
     assert _same_bits(y, want)
+
+
+def test_set_input_on_a_running_block(graph):
+    """setInput() of detail::hip_block (dsp/hip_block.h) on a live Squelch: source A (1+0j) -> Squelch -> sink, moved to source B
+    (2+0j) after 8 blocks of 4 096, 8 more blocks of B.  The harness fails on a block that mixes the two, on a block of A after one
+    of B, and on a sample that is neither."""
+    r = subprocess.run([BIN, "rebind", "4096", "8", "8"], check=True, timeout=60, capture_output=True, text=True)
+    assert "graph ok" in r.stdout, r.stdout + r.stderr

@@ -201,8 +201,8 @@ _SURFACE_SRC = r"""
 using namespace dsp;
 static_assert(std::is_same<decltype(Squelch::out), stream<complex_t>>::value, "Squelch::out");
 static_assert(std::is_same<decltype(AGC::out), stream<float>>::value, "AGC::out");
-static_assert(std::is_base_of<generic_block<Squelch>, Squelch>::value, "generic_block<Squelch>");
-static_assert(std::is_base_of<generic_block<AGC>, AGC>::value, "generic_block<AGC>");
+static_assert(std::is_base_of<detail::hip_block<complex_t, complex_t>, Squelch>::value, "the shared base of the HIP-backed blocks");
+static_assert(std::is_base_of<detail::hip_block<float, float>, AGC>::value, "the shared base of the HIP-backed blocks");
 float use(stream<complex_t>* iq, stream<float>* in) {
     Squelch a(iq, -30.0f);
     a.setLevel(-42.5f); a.setInput(iq);
@@ -225,7 +225,7 @@ def test_squelch_and_agc_blocks_compile_with_the_reference_surface(tmp_path):
     (tmp_path / "s.cpp").write_text(_SURFACE_SRC)
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Wno-unused-parameter", "-I", HOST,
                            "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.cpp")])
-    src = open(os.path.join(HOST, "dsp", "processing.h")).read()
+    src = open(os.path.join(HOST, "dsp", "processing.h")).read() + open(os.path.join(HOST, "dsp", "hip_block.h")).read()    # (the link protocol is the base's)
     for name in ("class Squelch", "class AGC", "claimConsumer", "done.arm", "qdsp_hip_squelch_process_ex", "qdsp_hip_agc_process_ex",
                  "linkIn()"):
         assert name in src, name

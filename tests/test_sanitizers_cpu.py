@@ -2,7 +2,7 @@
 the test pool and not wanted).
 
 * the block-graph mirror (qdsp_amd/host/dsp: stream hand-offs, device-resident links, Splitter banks, live retunes) runs its
-  graph_check harness against a TEST-ONLY fake libqdsp_hip (tests/fake_hip/fake_qdsp_hip.cpp: same C ABI, every operator a copy on
+  graph_check and demod_check harnesses against a TEST-ONLY fake libqdsp_hip (tests/fake_hip/fake_qdsp_hip.cpp: same C ABI, every operator a copy on
   the calling thread) built with -fsanitize=thread and with -fsanitize=address,undefined;
 * qdsp_amd/csrc/knobs.cpp: readers against concurrent reloads under -fsanitize=thread;
 * qdsp_amd/csrc/ring.cpp: the halo ring's buffer rotation against a fake synchronous HIP runtime + one-rank RCCL under
@@ -42,15 +42,16 @@ def cxx(args, cwd=FAKE):
 
 @pytest.fixture(scope="module", params=sorted(SAN))
 def graph(request):
-    """graph_check + the fake library, both built with one sanitizer."""
+    """graph_check, demod_check and the fake library, all built with one sanitizer."""
     tag = request.param
     out = os.path.join(FAKE, "build", tag)
     os.makedirs(out, exist_ok=True)
     flags = BASE + [f"-fsanitize={SAN[tag]}"]
     cxx(flags + ["-fPIC", "-shared", "-o", os.path.join(out, "libqdsp_hip.so"), "fake_qdsp_hip.cpp"])
-    cxx(flags + ["-Wall", "-pthread", f"-I{HOST}", f"-I{os.path.join(ROOT, 'include')}", "-o", os.path.join(out, "graph_check"),
-                 os.path.join(HOST, "examples", "graph_check.cpp"), f"-L{out}", "-lqdsp_hip", "-Wl,-rpath,$ORIGIN"])
-    return tag, os.path.join(out, "graph_check")
+    for prog in ("graph_check", "demod_check"):
+        cxx(flags + ["-Wall", "-pthread", f"-I{HOST}", f"-I{os.path.join(ROOT, 'include')}", "-o", os.path.join(out, prog),
+                     os.path.join(HOST, "examples", prog + ".cpp"), f"-L{out}", "-lqdsp_hip", "-Wl,-rpath,$ORIGIN"])
+    return tag, out
 
 
 @pytest.fixture(scope="module")
@@ -96,10 +97,46 @@ GRAPHS = [
 
 @pytest.mark.parametrize("args", GRAPHS, ids=[" ".join(a[:1] + a[-1:]) if a[0] == "splitretune" else a[0] + ("_" + a[1] if a[0] == "bench" else "") for a in GRAPHS])
 def test_block_graph_is_clean_under_sanitizers(graph, files, args):
-    tag, exe = graph
-    out = run_clean([exe] + args, cwd=files, extra_env={"FAKE_HIP_JITTER": "1"})
+    tag, build = graph
+    out = run_clean([os.path.join(build, "graph_check")] + args, cwd=files, extra_env={"FAKE_HIP_JITTER": "1"})
     if args[0] not in ("stream", "bench"):
         assert "graph ok" in out or "ok" in out, out[-500:]
+
+
+# source -> VFO -> the blocks of demodulator.h, deemp.h, pll.h and the level blocks of processing.h, in blocks of 24 000: the VFO
+# gives 2 400 a block, above the 1 024 the FeedForwardAGC graph needs
+VFO_ARGS = ["x.cf32", "yd", "24000", "300000", "2400000", "240000", "200000"]
+DEMODS = [
+    ["fm", "75000"],
+    ["fms", "75000"],
+    ["am"],
+    ["ssb", "3000", "0"],
+    ["ssb", "3000", "1"],
+    ["ssb", "3000", "2"],
+    ["deemp", "75000", "50e-6"],
+    ["squelch", "-50"],
+    ["agc", "20"],
+    ["ffagc"],
+    ["cagc", "1.0", "65536", "1e-3"],
+    ["costas", "2", "0.01"],
+    ["costas", "4", "0.01"],
+    ["costas", "8", "0.01"],
+]
+DEMOD_GRAPHS = [[d[0], link] + VFO_ARGS + d[1:] for d in DEMODS for link in ("dev", "host")]
+DEMOD_GRAPHS += [["sfm", "x.cf32", "yd", "24000", "240000", "75000"], ["rebind", "4096", "8", "8"]]
+
+
+def demod_id(a):
+    return "_".join([a[0]] + ([a[1]] if a[1] in ("dev", "host") else []) + (a[-2:-1] if a[0] == "costas" else a[-1:] if a[0] == "ssb" else []))
+
+
+@pytest.mark.parametrize("args", DEMOD_GRAPHS, ids=[demod_id(a) for a in DEMOD_GRAPHS])
+def test_demod_graph_is_clean_under_sanitizers(graph, files, args):
+    """demod_check against the fake library: every block built on detail::hip_block (dsp/hip_block.h) in a device-linked and a
+    host-linked graph, StereoFMDemod, and setInput() on a running block (`rebind`)."""
+    tag, build = graph
+    out = run_clean([os.path.join(build, "demod_check")] + args, cwd=files, extra_env={"FAKE_HIP_JITTER": "1"})
+    assert "graph ok" in out, out[-500:]
 
 
 def test_knob_table_readers_against_reloads_under_tsan():
