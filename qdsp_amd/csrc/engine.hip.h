@@ -91,8 +91,8 @@ struct Engine {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // overlap-save fast convolution (FIR<complex_t> with many taps), fft_fir.hip.h
     int fir_mode = 0;           // 0 auto, 1 direct form, 2 overlap-save FFT
-    float2* d_fft_H = nullptr;  // spectrum of the reversed taps / F, digit-reversed
-    float2* d_fft_TA = nullptr;
+    float2* d_fft_H = nullptr;  // spectrum of the reversed taps / F, digit-reversed: [256][16], then the same entry-major [16][256]
+    float2* d_fft_TA = nullptr; // pass-A twiddles, in the same two layouts
     float2* d_fft_TB = nullptr;
     int fft_ntaps = -1;         // tap count d_fft_H was built for (-1: not built)
     bool fft_tw_ready = false, f1k_tw_ready = false;   // twiddle tables allocated AND uploaded (set last: a failed first call retries them)

@@ -32,7 +32,12 @@
 //     segments moved to even starts: 248 VGPRs, decim-8 0.36 ms vs 0.33 ms with 8-byte loads;
 //   * non-temporal loads/stores for the sample stream: +-1 %;
 //   * pruning the inverse inside one segment for decimators (256/DEC active lanes): no faster
-//     than the full inverse -> the grouped kernel below.
+//     than the full inverse -> the grouped kernel below;
+//   * (fir_fft_dma_kernel) the first segment's LDS-DMA requested before the table loads instead of after them: 0.4176 against
+//     0.4174 ms with the entry-major tables, 0.488 against 0.471 ms with the lane-major ones (profiles/r05_fir256_ab.txt);
+//   * (fir_fft_dma_kernel) equal persistent workgroups, 4 / 8 / 16 queued per CU: 0.429 / 0.420 / 0.419 ms against 0.407 ms for the
+//     tapered grid (fft_fir.hip.h) in the same process -- with equal workgroups the chip ran partly empty for the last 18 % of the
+//     launch (profiles/r05_fir256_timeline_parent.txt), with the tapered grid for 3 %.
 //
 // Own translation unit because it is compiled with -fno-slp-vectorize: left on, clang's SLP
 // pass packs the butterflies' re/im arithmetic into v_pk_add/mul/fma_f32 and pays for it
@@ -56,6 +61,21 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // 2l'+1) contiguous and the pass-B reads (16 consecutive elements per 16 lanes) conflict-free:
 // evens on banks 16j.., odds +16, the next k0 row (+544 dwords) +32.
 __host__ __device__ constexpr int pos1(int e) { return (e >> 1) + 136 * (e & 1); }
+
+// The per-lane tables Hf and TA in the layout FftArgs::tbl names: entry k of lane / element i is (hf + k * ks)[i * ls] -- ONE load sequence
+// with run-time strides (two literal sequences behind a branch cost fir_fft_dma_kernel 12 bytes of scratch per lane).  Entry-major
+// ([16][256], the default): the lanes of a wave own 64 neighbouring elements under every lane-to-element map below, so one wave
+// instruction reads 512 contiguous bytes.  Lane-major ([256][16], QDSP_HIP_FFT_TBL=0): neighbouring lanes are 128 bytes apart -- 64
+// cache lines per instruction, each needed again by the next seven entries; 16 waves per CU doing that at once evict one another's
+// lines (profiles/r03_pmc_fir_fft_dma_kernel.json: 40 % of the kernel's L2 read requests were table reads).  Same values, same order of use.
+struct FftTbl {
+    const float2 *hf, *ta;
+    int ks;
+    unsigned ls;
+};
+__device__ __forceinline__ FftTbl fft_tbl(const FftArgs& a) {
+    return a.tbl ? FftTbl{a.HfT, a.TAT, 256, 1u} : FftTbl{a.Hf, a.TA, 1, 16u};
+}
 
 // Overlap-save block filter (see fft_fir.hip.h):
 //   DEC == 1 : FIR<complex_t>            y[n]  = sum_k taps[k] s[n - (N-1) + k]
@@ -125,11 +145,12 @@ __global__ __launch_bounds__(kFftNT, (DEC == 1 || !ROT) ? 4 : 3) void fir_fft_ke
     // DEC == 1 keeps both tables in VGPRs (124 in all).  The pruned-inverse variants need a
     // few more live values, so they re-read the pass-A twiddles from the L2-resident table
     // every block (opaque pointer below) rather than spill.
+    const FftTbl T = fft_tbl(a);
     float2 ta[16], hf[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        hf[k] = a.Hf[t * 16 + k];
-        if (DEC == 1) ta[k] = a.TA[te * 16 + k];
+        hf[k] = (T.hf + k * T.ks)[(unsigned)t * T.ls];
+        if (DEC == 1) ta[k] = (T.ta + k * T.ks)[(unsigned)te * T.ls];
     }
     // pass-A' twiddles of the pruned inverse: lane w = n1*NS + s <-> element n1*16 + s*DEC.
     // Re-read from the (L2-resident) table every block by the 256/DEC active lanes instead of
@@ -249,10 +270,11 @@ __global__ __launch_bounds__(kFftNT, (DEC == 1 || !ROT) ? 4 : 3) void fir_fft_ke
         // ---- pass A (over n2) + twiddle W4096^(t*k0) -----------------------------------
         fft16<false>(v);
         if constexpr (DEC > 1) {
-            const float2* tap = a.TA + te * 16;
-            asm volatile("" : "+v"(tap) : "v"(v[0].x));  // opaque + ordered after the butterflies
+            unsigned tap = (unsigned)te * T.ls;
+            int ks = T.ks;
+            asm volatile("" : "+v"(tap), "+s"(ks) : "v"(v[0].x));  // opaque + ordered after the butterflies (ks: the entries' addresses are formed here, not held in SGPRs across the loop)
 #pragma unroll
-            for (int k = 1; k < 16; k++) ta[k] = tap[k];
+            for (int k = 1; k < 16; k++) ta[k] = (T.ta + k * ks)[tap];
         }
         __syncthreads();  // previous block's last LDS reads are done
 #pragma unroll
@@ -407,12 +429,13 @@ __global__ __launch_bounds__(kFftNT, (DEC == 1 || !ROT) ? 4 : 3) void fir_fft_ke
             }
             __syncthreads();
             if (t < NACT) {  // lane w = n1*NS + s : twiddle, pass A' over k0, store
-                const float2* ta2 = a.TA + e0 * 16;
-                asm volatile("" : "+v"(ta2) : "v"(v[0].x));  // opaque: not hoisted out of the block loop, not issued early
+                unsigned ta2 = (unsigned)e0 * T.ls;
+                int ks = T.ks;
+                asm volatile("" : "+v"(ta2), "+s"(ks) : "v"(v[0].x));  // opaque: not hoisted out of the block loop, not issued early
 #pragma unroll
                 for (int k = 0; k < 16; k++) {
                     const float2 e = lds[t * kFftRow2 + k];
-                    v[k] = (k == 0) ? e : cmulc<true>(e, ta2[k]);
+                    v[k] = (k == 0) ? e : cmulc<true>(e, (T.ta + k * ks)[ta2]);
                 }
                 fft16<true>(v);
                 make_q();
@@ -450,9 +473,34 @@ __global__ __launch_bounds__(kFftNT, (DEC == 1 || !ROT) ? 4 : 3) void fir_fft_ke
 //     (the in-place ds_write_b64 of pass A is 2-way conflicted: 8 LDS cycles against the 6 the instruction takes anyway)
 //     and lets a v_permlane16_swap build the 16-byte stores.
 // Segments that touch the history or the end of the input take guarded loads into registers as in fir_fft_kernel.
+// Which segments a workgroup takes: fft_run_of (the tapered grid of fft_fir.hip.h) -- long workgroups stride through the call, short
+// ones take what is left in shrinking contiguous runs.
 // The DMA instruction is inline asm (it must not enter hipcc's own vmcnt bookkeeping, which would drain it together with
 // the stores at the next barrier): M0 is saved and restored inside the statement (cdna_hip_programming.md 5.7).
 #define QK_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+
+// The segments of workgroup w (fft_fir.hip.h, tapered grid): b, b + step, ... -- `left` of them.  Wave-uniform: scalar code.
+__device__ __forceinline__ void fft_run_of(const FftArgs& a, int w, int& b, int& step, int& left) {
+    if (w < a.n_long) {
+        b = w;
+        step = a.n_long;
+        left = (a.nblocks - w + a.n_long - 1) / a.n_long;
+        if (left > a.rounds) left = a.rounds;
+        return;
+    }
+    int seg = a.rounds * a.n_long, wg = a.n_long, rem = a.nblocks - seg, len = 1;
+    while (rem > 0) {
+        int cnt;
+        len = fft_taper_tier(rem, a.n_long, cnt);
+        if (w < wg + cnt) break;
+        wg += cnt;
+        seg += cnt * len;
+        rem -= cnt * len;
+    }
+    b = seg + (w - wg) * len;
+    step = 1;
+    left = a.nblocks - b < len ? a.nblocks - b : len;
+}
 
 __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a) {
     __shared__ __attribute__((aligned(16))) float2 lds[kFftLdsElems + 16 * 17];
@@ -473,24 +521,6 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
         }
         return;
     }
-    float2 ta[16], hf[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        hf[k] = a.Hf[t * 16 + k];
-        ta[k] = a.TA[te * 16 + k];
-    }
-    tbl[(t >> 4) * 17 + (t & 15)] = a.TB[t];
-    const float2* tb = tbl + lo * 17;
-    // the table loads are waited for HERE: left to hipcc, the wait (vmcnt(0): stores and DMA included) lands at their
-    // first use, inside the segment loop
-    {
-        float touch = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 16; k++) touch += hf[k].x + hf[k].y + (k ? ta[k].x + ta[k].y : 0.0f);
-        asm volatile("" ::"v"(touch));
-    }
-    __syncthreads();
-
     // this wave's 64 columns of row 0 as an LDS byte address, its first column, and the lane's byte offset in a row request
     const int wcol = __builtin_amdgcn_readfirstlane(t & ~63);
     const unsigned lds_cols = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds) + (unsigned)wcol * 8u;
@@ -508,13 +538,34 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
         }
     };
 
-    int b = blockIdx.x;
+    const FftTbl T = fft_tbl(a);
+    float2 ta[16], hf[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        hf[k] = (T.hf + k * T.ks)[(unsigned)t * T.ls];
+        ta[k] = (T.ta + k * T.ks)[(unsigned)te * T.ls];
+    }
+    tbl[(t >> 4) * 17 + (t & 15)] = a.TB[t];
+    const float2* tb = tbl + lo * 17;
+    // the table loads are waited for HERE: left to hipcc, the wait (vmcnt(0): stores and DMA included) lands at their
+    // first use, inside the segment loop
+    {
+        float touch = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; k++) touch += hf[k].x + hf[k].y + (k ? ta[k].x + ta[k].y : 0.0f);
+        asm volatile("" ::"v"(touch));
+    }
+    __syncthreads();
+    // (Requesting the first segment BEFORE the tables, so that its HBM round trip runs beside the table loads: 0.4176 against 0.4174 ms
+    // with the entry-major tables, slower with the lane-major ones -- profiles/r05_fir256_ab.txt -- so the order stays as it was.)
+    int b, step, left;
+    fft_run_of(a, blockIdx.x, b, step, left);
     bool landed_in_lds = false, eight_younger = false;
-    if (b < a.nblocks && is_interior(b)) {
+    if (left > 0 && is_interior(b)) {
         request(b);
         landed_in_lds = true;
     }
-    for (; b < a.nblocks; b += a.nwg) {
+    for (; left > 0; left--, b += step) {
         const long long seg0 = seg_start(b);
         float2 v[16];
         if (landed_in_lds) {
@@ -582,8 +633,8 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
 #pragma unroll
         for (int k = 0; k < 16; k++) e[k] = lds[k * kFftRow1 + te];
         // ---- the next segment's samples: requested now, into the columns this wave has just read ---------------------
-        const int nb = b + a.nwg;
-        landed_in_lds = is_interior(nb);
+        const int nb = b + step;
+        landed_in_lds = left > 1 && is_interior(nb);
         if (landed_in_lds) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads above have returned
             request(nb);
@@ -634,7 +685,9 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
 // hipcc folds whole-vector negation only) -- instead of 2 v_mul + 2 v_fmac.
 // STAMPS: diagnostic build (never shipped to a caller: launch_fir_fft takes it only when FftArgs::stamps is set, which only
 // scripts/stamp_fir_fft.py does): every wave sums, per phase of the segment loop, the shader-clock ticks (s_memtime) it
-// spent there; wave 0 of each workgroup writes its sixteen sums to stamps[blockIdx.x * 16 ..].  Nothing is computed from them.
+// spent there; wave 0 of each workgroup writes its sixteen sums to stamps[blockIdx.x * kFftStampWords ..], followed by the workgroup's
+// first tick, its tick at loop entry and its last tick on the constant-rate clock (s_memrealtime: the same on every CU) and the ids of
+// the CU it ran on -- the launch's timeline: prologue share, hand-over gaps on a slot, ramp and tail.  Nothing is computed from them.
 template <bool CONJ, int ABL> __device__ __forceinline__ v2f abl_cmul(v2f a, v2f b) {
     if (ABL & 1) return a;
     return pk_cmul2<CONJ>(a, b);
@@ -646,6 +699,8 @@ template <bool STAMPS, int ABL = 0>
 __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs a) {
     __shared__ __attribute__((aligned(16))) v2f lds[kFftLdsElems + 16 * 17];
     v2f* tbl = lds + kFftLdsElems;  // pass-B twiddles W256^(lo*k), rows padded to 17
+    unsigned long long rt_first = 0;
+    if constexpr (STAMPS) rt_first = __builtin_amdgcn_s_memrealtime();
     const int t = threadIdx.x;
     const int hi = t >> 4, lo = t & 15;
     const int H = a.H;
@@ -662,24 +717,6 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
         }
         return;
     }
-    v2f ta[16], hf[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        hf[k] = reinterpret_cast<const v2f*>(a.Hf)[t * 16 + k];
-        ta[k] = reinterpret_cast<const v2f*>(a.TA)[te * 16 + k];
-    }
-    tbl[(t >> 4) * 17 + (t & 15)] = reinterpret_cast<const v2f*>(a.TB)[t];
-    const v2f* tb = tbl + lo * 17;
-    // the table loads are waited for HERE: left to hipcc, the wait (vmcnt(0): stores and DMA included) lands at their
-    // first use, inside the segment loop
-    {
-        float touch = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 16; k++) touch += hf[k].x + hf[k].y + (k ? ta[k].x + ta[k].y : 0.0f);
-        asm volatile("" ::"v"(touch));
-    }
-    __syncthreads();
-
     // this wave's 64 columns of row 0 as an LDS byte address, its first column, and the lane's byte offset in a row request
     const int wcol = __builtin_amdgcn_readfirstlane(t & ~63);
     const unsigned lds_cols = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds) + (unsigned)wcol * 8u;
@@ -705,22 +742,45 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
         }
     };
 
+    const FftTbl T = fft_tbl(a);
+    v2f ta[16], hf[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        hf[k] = reinterpret_cast<const v2f*>(T.hf + k * T.ks)[(unsigned)t * T.ls];
+        ta[k] = reinterpret_cast<const v2f*>(T.ta + k * T.ks)[(unsigned)te * T.ls];
+    }
+    tbl[(t >> 4) * 17 + (t & 15)] = reinterpret_cast<const v2f*>(a.TB)[t];
+    const v2f* tb = tbl + lo * 17;
+    // the table loads are waited for HERE: left to hipcc, the wait (vmcnt(0): stores and DMA included) lands at their
+    // first use, inside the segment loop
+    {
+        float touch = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; k++) touch += hf[k].x + hf[k].y + (k ? ta[k].x + ta[k].y : 0.0f);
+        asm volatile("" ::"v"(touch));
+    }
+    __syncthreads();
+
     unsigned acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tick = 0;
-    if constexpr (STAMPS) tick = __builtin_amdgcn_s_memtime();
+    unsigned long long tick = 0, rt_loop = 0;
+    if constexpr (STAMPS) {
+        tick = __builtin_amdgcn_s_memtime();
+        rt_loop = __builtin_amdgcn_s_memrealtime();
+    }
 #define QK_STAMP(i)                                                          \
     if constexpr (STAMPS) {                                                  \
         const unsigned long long now_ = __builtin_amdgcn_s_memtime();        \
         acc[i] += (unsigned)(now_ - tick);                                   \
         tick = now_;                                                         \
     }
-    int b = blockIdx.x;
+    int b, step, left;
+    fft_run_of(a, blockIdx.x, b, step, left);
     bool landed_in_lds = false, eight_younger = false;
-    if (b < a.nblocks && is_interior(b)) {
+    if (left > 0 && is_interior(b)) {
         request(b);
         landed_in_lds = true;
     }
-    for (; b < a.nblocks; b += a.nwg) {
+    for (; left > 0; left--, b += step) {
         const long long seg0 = seg_start(b);
         v2f v[16];
         QK_STAMP(15)   // pass A', stores, loop control
@@ -804,8 +864,8 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
 #pragma unroll
         for (int k = 0; k < 16; k++) e[k] = lds[k * kFftRow1 + te];
         // ---- the next segment's samples: requested now, into the columns this wave has just read ---------------------
-        const int nb = b + a.nwg;
-        landed_in_lds = is_interior(nb);
+        const int nb = b + step;
+        landed_in_lds = left > 1 && is_interior(nb);
         if (landed_in_lds) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads above have returned
             request(nb);
@@ -853,8 +913,16 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if constexpr (STAMPS) {
         if (t == 0) {
+            unsigned* st = a.stamps + (long long)blockIdx.x * kFftStampWords;
 #pragma unroll
-            for (int q = 0; q < 16; q++) a.stamps[(long long)blockIdx.x * 16 + q] = acc[q];
+            for (int q = 0; q < 16; q++) st[q] = acc[q];
+            // the workgroup's place on the launch's timeline, on the constant-rate clock (comparable between CUs), and where it ran
+            const unsigned long long rt_last = __builtin_amdgcn_s_memrealtime();
+            st[16] = (unsigned)rt_first; st[17] = (unsigned)(rt_first >> 32);
+            st[18] = (unsigned)rt_loop;  st[19] = (unsigned)(rt_loop >> 32);
+            st[20] = (unsigned)rt_last;  st[21] = (unsigned)(rt_last >> 32);
+            st[22] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_ID: wave, SIMD, CU, SH, SE
+            st[23] = __builtin_amdgcn_s_getreg((3 << 11) | 20);    // XCC_ID
         }
     }
 #undef QK_STAMP
@@ -903,14 +971,15 @@ __global__ __launch_bounds__(kFftNT, 2) void fir_fft_dec_kernel(const FftArgs a)
 
     // per-lane constants kept in registers: forward twiddles and the lane's spectrum slice; the
     // inverse-pass twiddles (used once per group) are re-read from the L2-resident table
+    const FftTbl T = fft_tbl(a);
     float2 ta[16], hf[16];
     // inverse-pass lane w = bb*NACT + n1*NS + s  <->  element e0 = n1*16 + s*DEC of segment bb
     const int wbb = t / NACT, wr = t % NACT;
     const int e0 = (wr / NS) * 16 + (wr % NS) * DEC;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        hf[k] = a.Hf[t * 16 + k];
-        ta[k] = a.TA[t * 16 + k];
+        hf[k] = (T.hf + k * T.ks)[(unsigned)t * T.ls];
+        ta[k] = (T.ta + k * T.ks)[(unsigned)t * T.ls];
     }
     tbl[(t >> 4) * 17 + (t & 15)] = a.TB[t];
     const float2* tb = tbl + lo * 17;
@@ -1039,12 +1108,13 @@ __global__ __launch_bounds__(kFftNT, 2) void fir_fft_dec_kernel(const FftArgs a)
         __syncthreads();
         // ---- pass A' (lane w = bb*NACT + n1*NS + s, over k0) and store -----------------------------
         {
-            const float2* ta2 = a.TA + e0 * 16;
-            asm volatile("" : "+v"(ta2) : "v"(v[0].x));  // opaque: re-read per group, after pass B'
+            unsigned ta2 = (unsigned)e0 * T.ls;
+            int ks = T.ks;
+            asm volatile("" : "+v"(ta2), "+s"(ks) : "v"(v[0].x));  // opaque: re-read per group, after pass B'
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const float2 e = lds[t * kFftRow2 + k];
-                v[k] = (k == 0) ? e : cmulc<true>(e, ta2[k]);
+                v[k] = (k == 0) ? e : cmulc<true>(e, (T.ta + k * ks)[ta2]);
             }
         }
         fft16<true>(v);

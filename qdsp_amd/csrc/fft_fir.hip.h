@@ -24,6 +24,8 @@ constexpr int kFftRow1 = 272;   // layout 1: [k0][n1*16 + n0], row padded 256 ->
 constexpr int kFftRow2 = 17;    // layout 2: [k0*16 + k1][n0], row padded 16 -> 17 elements
 constexpr int kFftLdsElems = 16 * kFftRow1;  // 4352 >= 256*17 = 4352
 
+constexpr int kFftStampWords = 24;   // per workgroup: 16 per-phase sums, first / loop-entry / last tick (64-bit each), HW_ID, XCC_ID
+
 struct FftArgs {
     const float2* in;
     float2* out;
@@ -34,6 +36,9 @@ struct FftArgs {
     const float2* Hf;         // [256][16]: Hf[(k0*16+k1)*16 + k2] = FFT(taps reversed)[k0 + 16 k1 + 256 k2] / F
     const float2* TA;         // [256][16]: exp(-j 2pi t k / 4096)
     const float2* TB;         // [16][16] : exp(-j 2pi lo k / 256)
+    const float2* HfT;        // [16][256]: Hf entry-major, HfT[k*256 + t] == Hf[t*16 + k] -- a wave reads 512 contiguous bytes per entry
+    const float2* TAT;        // [16][256]: TA entry-major, TAT[k*256 + element] == TA[element*16 + k]
+    int tbl;                  // 1: the kernels read HfT / TAT (the default); 0: Hf / TA (QDSP_HIP_FFT_TBL=0, kept for the A/B of the two layouts)
     long long count;          // input samples of this call
     long long nout;           // outputs of this call
     int H;                    // history length (ntaps-1 for the FIR, taps per phase for the resampler)
@@ -47,11 +52,13 @@ struct FftArgs {
     int L;                    // stream positions covered per segment = 4096 - ov
     int nblocks;
     int nwg;                  // persistent workgroups (grid = nwg + 1; the last one hands over history)
+    int n_long, rounds;       // the LDS-DMA kernels: workgroups below n_long take segments w, w + n_long, ... (at most `rounds` of them);
+                              // the nwg - n_long after them take short contiguous runs (fft_taper_tier); n_long == nwg: no short ones
     int vec;                  // 1: in/out 16-byte aligned and segments start on even samples -> float4 path
     int grouped;              // dec >= 4: 1 = fir_fft_dec_kernel (groups of dec segments), 0 = one segment per workgroup
     int m_shift;              // fir_fft1k_kernel, strided: log2(decm) when decm is a power of two <= 64 (a lane keeps all or none of its 16 elements), else -1
     int abl;                  // diagnostic builds of fir_fft_dmapk_kernel: ablation mask (0: the product)
-    unsigned* stamps;         // diagnostic build of fir_fft_dmapk_kernel only: [grid][16] per-phase tick sums (nullptr: off)
+    unsigned* stamps;         // diagnostic build of fir_fft_dmapk_kernel only: [grid][kFftStampWords] per-phase tick sums + timeline (nullptr: off)
     int nt;                   // fir_fft_dmapk_kernel: bit 0 = non-temporal DMA of the rows no neighbour re-reads, bit 1 = non-temporal stores
     int dma;                  // 1: fir_fft_dma_kernel (FIR<complex_t>, 16-byte aligned in / out, overlap <= 2048): segments arrive by LDS-DMA
     int real2;                // 1: real samples (4-byte in/out/hist); block b = real segments 2b (re) and 2b+1 (im)
@@ -64,6 +71,38 @@ struct FftArgs {
     float2 wtab[16];          // exp(j 2pi 256*n2*dphase)
     float gm1;                // |phase_inc| - 1 (VOLK magnitude sawtooth: a real scale of the input samples), 0 = off
 };
+
+// Tapered grid of the LDS-DMA kernels.  `slots` workgroups are resident at a time; a grid of equal workgroups ends with slots that find
+// no successor while others still work through a whole one.  Here the first min(nblocks, slots) workgroups are long -- `rounds`
+// stride-n_long segments each, three quarters of the whole rounds the call has, so the front stays compact and they pay one prologue
+// -- and the rest of the segments goes to short workgroups in tiers: every workgroup of a tier takes `len` consecutive segments,
+// len = 1/(2 slots) of what is left, rounded up, so the runs shrink to single segments at the end and the dispatcher hands them to
+// whichever slot frees up first.  A function of nblocks and slots alone (2^27 samples at 256 taps: 34 953 segments = 1024 x 26 and
+// 3 209 short workgroups of 5, 2 and 1); host (grid size) and kernel (a workgroup's run) walk the same tiers.
+// (the long workgroups' share, measured at 2^27 samples in one process: 17 / 26 / 30 / 32 / 33 of the 34 rounds 0.430 / 0.423 / 0.426 /
+// 0.439 / 0.443 ms -- the slots drift apart by more than a few segments, and only short workgroups even that out)
+inline int fft_taper_rounds(int nblocks, int slots) {
+    if (nblocks <= slots) return 1;
+    return nblocks / slots - nblocks / (4 * slots);
+}
+// one tier: `rem` segments are left; returns the tier's run length and sets its workgroup count
+__host__ __device__ inline int fft_taper_tier(int rem, int slots, int& cnt) {
+    const int len = (rem + 2 * slots - 1) / (2 * slots);
+    cnt = (rem + len - 1) / len;
+    if (cnt > slots) cnt = slots;
+    return len;
+}
+inline int fft_taper_short_count(int nblocks, int slots, int rounds) {
+    const int n_long = nblocks < slots ? nblocks : slots;
+    int rem = nblocks - rounds * n_long, total = 0;
+    while (rem > 0) {
+        int cnt;
+        const int len = fft_taper_tier(rem, slots, cnt);
+        total += cnt;
+        rem -= cnt * len;
+    }
+    return total;
+}
 
 // fft1k_fir.hip: 1024-point segments, one wave each (reference-sized calls).  Same FftArgs; Hf / TA / TB point at
 // that kernel's own tables (entry-major: [16][64] spectrum in its pass-C order, [16][64] W1024^(l ka), [16][4] W64^(j kb1)),

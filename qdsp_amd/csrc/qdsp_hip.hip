@@ -638,29 +638,31 @@ int fft_prepare(Engine* e) {
     const int N = e->ntaps;
     // g[j] = taps[N-1-j]:  c[p] = sum_j g[j] s[p-j] = sum_k taps[k] s[p-(N-1)+k];
     // Hf[k] = sum_j g[j] exp(-j 2pi jk/F) / F
-    std::vector<float2> Hp(F), TA(256 * 16), TB(16 * 16);
+    // Hf and TA are uploaded twice, behind each other in one allocation: lane-major [256][16] (QDSP_HIP_FFT_TBL=0) and entry-major
+    // [16][256] -- the same values; the lanes of a wave read 512 contiguous bytes of the second per instruction (FftArgs::HfT / TAT)
+    std::vector<float2> Hp(2 * F), TA(2 * 256 * 16), TB(16 * 16);
     std::vector<long double> gr(N), gi(N);
     reversed_taps(e, gr, gi);
     std::vector<double> sre, sim;
     host_spectrum(gr, gi, F, sre, sim);
     for (int k = 0; k < F; k++) {
         const int k0 = k & 15, k1 = (k >> 4) & 15, k2 = k >> 8;
-        Hp[(k0 * 16 + k1) * 16 + k2] = make_float2((float)(sre[k] / F), (float)(sim[k] / F));
+        Hp[(k0 * 16 + k1) * 16 + k2] = Hp[F + k2 * 256 + (k0 * 16 + k1)] = make_float2((float)(sre[k] / F), (float)(sim[k] / F));
     }
     if (!e->fft_tw_ready) {
         for (int t = 0; t < 256; t++)
-            for (int k = 0; k < 16; k++) TA[t * 16 + k] = make_float2((float)cs[(t * k) % F], (float)(-sn[(t * k) % F]));
+            for (int k = 0; k < 16; k++) TA[t * 16 + k] = TA[F + k * 256 + t] = make_float2((float)cs[(t * k) % F], (float)(-sn[(t * k) % F]));
         for (int lo = 0; lo < 16; lo++)
             for (int k = 0; k < 16; k++) TB[lo * 16 + k] = make_float2((float)cs[(16 * lo * k) % F], (float)(-sn[(16 * lo * k) % F]));
-        if (!e->d_fft_H) HIPCHK(hipMalloc(&e->d_fft_H, sizeof(float2) * F));
-        if (!e->d_fft_TA) HIPCHK(hipMalloc(&e->d_fft_TA, sizeof(float2) * 256 * 16));
+        if (!e->d_fft_H) HIPCHK(hipMalloc(&e->d_fft_H, sizeof(float2) * 2 * F));
+        if (!e->d_fft_TA) HIPCHK(hipMalloc(&e->d_fft_TA, sizeof(float2) * 2 * 256 * 16));
         if (!e->d_fft_TB) HIPCHK(hipMalloc(&e->d_fft_TB, sizeof(float2) * 16 * 16));
         HIPCHK(hipMemcpy(e->d_fft_TA, TA.data(), sizeof(float2) * TA.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d_fft_TB, TB.data(), sizeof(float2) * TB.size(), hipMemcpyHostToDevice));
         e->fft_tw_ready = true;
     }
     HIPCHK(hipDeviceSynchronize());   // (retune / new taps: nothing in flight may still read the old spectrum)
-    HIPCHK(hipMemcpy(e->d_fft_H, Hp.data(), sizeof(float2) * F, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_fft_H, Hp.data(), sizeof(float2) * Hp.size(), hipMemcpyHostToDevice));
     e->fft_ntaps = N;
     e->fft_dphase = key_dphase;
     return 0;
@@ -999,6 +1001,9 @@ int launch_fft(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d
     a.Hf = e->d_fft_H;
     a.TA = e->d_fft_TA;
     a.TB = e->d_fft_TB;
+    a.HfT = e->d_fft_H + qk::kFftN;
+    a.TAT = e->d_fft_TA + qk::kFftN;
+    a.tbl = qk::knob(qk::K_FFT_TBL, 1) ? 1 : 0;
     a.count = count;
     a.nout = nout;
     a.H = e->H;
@@ -1045,7 +1050,7 @@ int launch_fft(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d
         a.vec = ((((uintptr_t)d_in) | ((uintptr_t)d_out)) & 7) == 0;
         a.nblocks = (a.nblocks + 1) / 2;
     }
-    // FIR: 4 workgroups resident per CU (124 VGPRs, 37 KB LDS), 16 queued per CU for balance.
+    // FIR: 4 workgroups resident per CU (124 VGPRs, 37 KB LDS), 16 queued per CU for balance (the LDS-DMA kernels: a tapered grid, below).
     // Decimators work in groups of `dec` segments, 2 resident per CU (70 KB LDS).
     // (grouped only when the groups fill the chip -- measured crossover ~1000 groups, 2^25 samples at decimation 8 --
     // below that the segments run one per workgroup: a 1e6-sample block 10 us instead of 28)
@@ -1060,6 +1065,14 @@ int launch_fft(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d
     const int units = grouped ? (a.nblocks + a.dec - 1) / a.dec : a.nblocks;
     int nwg = 256 * per_cu;
     if (nwg > units) nwg = units;
+    a.n_long = nwg;   // (n_long, rounds: read by the LDS-DMA kernels only)
+    a.rounds = (units + nwg - 1) / (nwg > 0 ? nwg : 1);
+    if (a.dma) {   // tapered grid (fft_fir.hip.h): the resident workgroups (four per CU) are long, short ones follow
+        const int slots = 256 * qk::knob(qk::K_FFT_WG_PER_CU, 4);
+        a.n_long = a.nblocks < slots ? a.nblocks : slots;
+        a.rounds = qk::fft_taper_rounds(a.nblocks, slots);
+        nwg = a.n_long + qk::fft_taper_short_count(a.nblocks, slots, a.rounds);
+    }
     a.nwg = nwg;
     if (a.rot) {
         a.phase_in0 = e->phase;
