@@ -30,7 +30,8 @@
 //     translating decimator 0.46 vs 0.32 ms per 2^27 samples;
 //   * 16-byte loads by lane pairs (as fir_fft_kernel does) in the grouped decimator kernel, with
 //     segments moved to even starts: 248 VGPRs, decim-8 0.36 ms vs 0.33 ms with 8-byte loads;
-//   * non-temporal loads/stores for the sample stream: +-1 %;
+//   * non-temporal loads/stores for the sample stream of fir_fft_kernel<1>: +-1 % (its wait for the next loads also waits for the stores;
+//     the LDS-DMA kernels never wait for theirs and take the policy: round 6 below);
 //   * pruning the inverse inside one segment for decimators (256/DEC active lanes): no faster
 //     than the full inverse -> the grouped kernel below;
 //   * (fir_fft_dma_kernel) the first segment's LDS-DMA requested before the table loads instead of after them: 0.4176 against
@@ -38,6 +39,12 @@
 //   * (fir_fft_dma_kernel) equal persistent workgroups, 4 / 8 / 16 queued per CU: 0.429 / 0.420 / 0.419 ms against 0.407 ms for the
 //     tapered grid (fft_fir.hip.h) in the same process -- with equal workgroups the chip ran partly empty for the last 18 % of the
 //     launch (profiles/r05_fir256_timeline_parent.txt), with the tapered grid for 3 %.
+//   * (round 6, the LDS-DMA kernels' cache policy QDSP_HIP_FFT_NT, profiles/r06_fir256_ab.txt and r06_fir256_taps.txt; kept: non-temporal stores,
+//     with non-temporal DMA of rows 1-14 at overlaps up to 256 -- 0.4187 -> 0.4001 ms at 256 taps) rejected: the non-temporal DMA alone, slower at
+//     every overlap (0.4232 against 0.4187 ms); rows 0 and 15 non-temporal as well, 0.4102 against 0.4001 ms (alone 0.4327); either bit at an overlap
+//     that is no multiple of 8 samples (63 taps: 0.4357 / 0.4506 / 0.4233 against 0.4182 ms); the DMA bit at overlaps above 256 (2049 taps: 0.6626
+//     against 0.6472 ms with the stores alone); fir_fft_dmapk_kernel and 8 workgroup slots per CU under the winning policy: 0.4029 and 0.4018
+//     against 0.4001 ms, ranges overlapping.
 //
 // Own translation unit because it is compiled with -fno-slp-vectorize: left on, clang's SLP
 // pass packs the butterflies' re/im arithmetic into v_pk_add/mul/fma_f32 and pays for it
@@ -502,7 +509,13 @@ __device__ __forceinline__ void fft_run_of(const FftArgs& a, int w, int& b, int&
     left = a.nblocks - b < len ? a.nblocks - b : len;
 }
 
-__global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a) {
+// NT: the cache policy of the sample stream, a compile-time copy of FftArgs::nt (a run-time branch between two literal request
+// sequences is what cost this kernel its fourth workgroup per CU once: 128 VGPRs and 12 bytes of scratch).  Bit 0: the interior segments'
+// LDS-DMA of rows 1-14 is non-temporal (rows 0 and 15 hold the overlap a neighbouring segment reads as well and stay cacheable; bit 2,
+// diagnostic builds only, takes those two along); bit 1: the eight 16-byte stores are non-temporal.  The guarded path of the first and last
+// segments keeps plain accesses.  Same values in the same order: no bit of any output depends on NT.
+template <int NT>
+__device__ __forceinline__ void fir_fft_dma_body(const FftArgs& a) {
     __shared__ __attribute__((aligned(16))) float2 lds[kFftLdsElems + 16 * 17];
     float2* tbl = lds + kFftLdsElems;  // pass-B twiddles W256^(lo*k), rows padded to 17
     const int t = threadIdx.x;
@@ -534,7 +547,10 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
         const float2* src = a.in + seg_start(b) + wcol;
         if ((t & 32) == 0) {
 #pragma unroll
-            for (int n2 = 0; n2 < 16; n2++) dma16_to_lds(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
+            for (int n2 = 0; n2 < 16; n2++) {
+                if ((NT & 1) && ((NT & 4) || (n2 != 0 && n2 != 15))) dma16_to_lds_nt(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
+                else dma16_to_lds(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
+            }
         }
     };
 
@@ -656,8 +672,11 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
                 const auto sx = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo_row.x), __float_as_uint(hi_row.x), false, false);
                 const auto sy = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo_row.y), __float_as_uint(hi_row.y), false, false);
                 // now (x,y | z,w) = columns (te & ~1, +1) of row half*8 + r
-                if ((half * 8 + r) * 256 + (te & ~1) >= a.ov)   // ov is even: both elements or neither
-                    o4[pair + r * 128] = (f4v){__uint_as_float(sx[0]), __uint_as_float(sy[0]), __uint_as_float(sx[1]), __uint_as_float(sy[1])};
+                if ((half * 8 + r) * 256 + (te & ~1) >= a.ov) {   // ov is even: both elements or neither
+                    const f4v o = {__uint_as_float(sx[0]), __uint_as_float(sy[0]), __uint_as_float(sx[1]), __uint_as_float(sy[1])};
+                    if constexpr ((NT & 2) != 0) __builtin_nontemporal_store(o, o4 + pair + r * 128);
+                    else o4[pair + r * 128] = o;
+                }
             }
             eight_younger = true;   // (rows 8..15 always lie past the overlap: ov <= 2048 on this path, so all eight are issued)
         } else {
@@ -677,6 +696,10 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// The plain policy keeps its own, untemplated entry point (the name the resource table, the profiles and the tests know the kernel by).
+__global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_kernel(const FftArgs a) { fir_fft_dma_body<0>(a); }
+template <int NT> __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dma_nt_kernel(const FftArgs a) { fir_fft_dma_body<NT>(a); }
+
 // ---- fir_fft_dmapk_kernel: the same kernel with its complex arithmetic on packed FP32 pairs -------------------------------
 // PMC of fir_fft_dma_kernel (profiles/r03_pmc_fir_fft_dma_kernel.json): waits 39 % -> 20 % of the wave cycles, issue stalls 30 % ->
 // 45 %: with the memory waits gone the kernel is VALU-issue-bound at ~4.1 cycles per instruction (5261 instructions per segment).
@@ -695,7 +718,9 @@ template <bool CONJ, int ABL> __device__ __forceinline__ v2f abl_cmul(v2f a, v2f
 
 // ABL: ablations for profiles/r03_ablate_fir_fft_dmapk.txt (diagnostic builds): 1 = no arithmetic (the LDS exchanges, barriers, DMA and stores
 // stay), 2 = no global stores, 4 = no DMA (the segments are whatever lies in LDS).
-template <bool STAMPS, int ABL = 0>
+// NT: the sample stream's cache policy, as in fir_fft_dma_body (a compile-time copy of FftArgs::nt).  It was a run-time branch here at first, and
+// hipcc merged the plain and the non-temporal store of each row into ONE plain store -- bit 1 did nothing (profiles/r06_fir256_ab.txt).
+template <bool STAMPS, int ABL = 0, int NT = 0>
 __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs a) {
     __shared__ __attribute__((aligned(16))) v2f lds[kFftLdsElems + 16 * 17];
     v2f* tbl = lds + kFftLdsElems;  // pass-B twiddles W256^(lo*k), rows padded to 17
@@ -729,15 +754,10 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
     auto request = [&](int b) {   // rows 0..15 of segment b -> this wave's columns (lanes 0-31: 512 bytes per row)
         const float2* src = a.in + seg_start(b) + wcol;
         if ((t & 32) == 0 && !(ABL & 4)) {
-            if (a.nt & 1) {   // rows 0 and 15 hold the overlap the neighbouring segments read as well: those stay cacheable
 #pragma unroll
-                for (int n2 = 0; n2 < 16; n2++) {
-                    if (n2 == 0 || n2 == 15) dma16_to_lds(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
-                    else dma16_to_lds_nt(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
-                }
-            } else {
-#pragma unroll
-                for (int n2 = 0; n2 < 16; n2++) dma16_to_lds(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
+            for (int n2 = 0; n2 < 16; n2++) {   // rows 0 and 15 hold the overlap the neighbouring segments read as well: those stay cacheable
+                if ((NT & 1) && n2 != 0 && n2 != 15) dma16_to_lds_nt(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
+                else dma16_to_lds(src + n2 * 256, voff, lds_cols + (unsigned)(n2 * kFftRow1) * 8u);
             }
         }
     };
@@ -881,7 +901,6 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
             f4v* __restrict__ o4 = reinterpret_cast<f4v*>(a.out + seg0);   // wave-uniform; 16-byte units
             int pair = (te >> 1) + half * 8 * 128;
             asm volatile("" : "+v"(pair));   // (as above)
-            const bool nts = (a.nt & 2) != 0;
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const v2f lo_row = v[rev16(r)], hi_row = v[rev16(8 + r)];
@@ -891,7 +910,7 @@ __global__ __launch_bounds__(kFftNT, 4) void fir_fft_dmapk_kernel(const FftArgs 
                 if ((half * 8 + r) * 256 + (te & ~1) >= a.ov) {   // ov is even: both elements or neither
                     const f4v o = {__uint_as_float(sx[0]), __uint_as_float(sy[0]), __uint_as_float(sx[1]), __uint_as_float(sy[1])};
                     if (ABL & 2) { if (o.x == 1.2345e30f) o4[pair + r * 128] = o; }
-                    else if (nts) __builtin_nontemporal_store(o, o4 + pair + r * 128);
+                    else if constexpr ((NT & 2) != 0) __builtin_nontemporal_store(o, o4 + pair + r * 128);
                     else o4[pair + r * 128] = o;
                 }
             }
@@ -1133,6 +1152,16 @@ __global__ __launch_bounds__(kFftNT, 2) void fir_fft_dec_kernel(const FftArgs a)
     }
 }
 
+// the instantiation of FftArgs::nt
+template <bool STAMPS> static void launch_fir_fft_dmapk(const FftArgs& a, int grid, hipStream_t stream) {
+    switch (a.nt & 3) {
+        case 1: hipLaunchKernelGGL((fir_fft_dmapk_kernel<STAMPS, 0, 1>), dim3(grid), dim3(kFftNT), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((fir_fft_dmapk_kernel<STAMPS, 0, 2>), dim3(grid), dim3(kFftNT), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((fir_fft_dmapk_kernel<STAMPS, 0, 3>), dim3(grid), dim3(kFftNT), 0, stream, a); break;
+        default: hipLaunchKernelGGL((fir_fft_dmapk_kernel<STAMPS, 0, 0>), dim3(grid), dim3(kFftNT), 0, stream, a); break;
+    }
+}
+
 int launch_fir_fft(const FftArgs& a, int grid, hipStream_t stream) {
 #define QK_FFT(dec, rot) hipLaunchKernelGGL((fir_fft_dec_kernel<dec, rot>), dim3(grid), dim3(kFftNT), 0, stream, a)
     const bool r = a.rot != 0;
@@ -1144,11 +1173,22 @@ int launch_fir_fft(const FftArgs& a, int grid, hipStream_t stream) {
             else if (a.dma == 2 && a.abl == 4) hipLaunchKernelGGL((fir_fft_dmapk_kernel<false, 4>), dim3(grid), dim3(kFftNT), 0, stream, a);
             else if (a.dma == 2 && a.abl == 6) hipLaunchKernelGGL((fir_fft_dmapk_kernel<false, 6>), dim3(grid), dim3(kFftNT), 0, stream, a);
             else if (a.dma == 2 && a.abl == 7) hipLaunchKernelGGL((fir_fft_dmapk_kernel<false, 7>), dim3(grid), dim3(kFftNT), 0, stream, a);
-            else if (a.dma == 2 && a.stamps) hipLaunchKernelGGL(fir_fft_dmapk_kernel<true>, dim3(grid), dim3(kFftNT), 0, stream, a);
+            else if (a.dma == 2 && a.stamps) launch_fir_fft_dmapk<true>(a, grid, stream);
             else
 #endif
-            if (a.dma == 2) hipLaunchKernelGGL(fir_fft_dmapk_kernel<false>, dim3(grid), dim3(kFftNT), 0, stream, a);
-            else if (a.dma) hipLaunchKernelGGL(fir_fft_dma_kernel, dim3(grid), dim3(kFftNT), 0, stream, a);
+            if (a.dma == 2) launch_fir_fft_dmapk<false>(a, grid, stream);
+            else if (a.dma) {
+                switch ((a.nt & 1) ? a.nt & (QDSP_HIP_DIAG ? 7 : 3) : a.nt & 2) {
+                    case 1: hipLaunchKernelGGL(fir_fft_dma_nt_kernel<1>, dim3(grid), dim3(kFftNT), 0, stream, a); break;
+                    case 2: hipLaunchKernelGGL(fir_fft_dma_nt_kernel<2>, dim3(grid), dim3(kFftNT), 0, stream, a); break;
+                    case 3: hipLaunchKernelGGL(fir_fft_dma_nt_kernel<3>, dim3(grid), dim3(kFftNT), 0, stream, a); break;
+#if QDSP_HIP_DIAG   // rows 0 and 15 non-temporal as well (profiles/r06_fir256_ab.txt)
+                    case 5: hipLaunchKernelGGL(fir_fft_dma_nt_kernel<5>, dim3(grid), dim3(kFftNT), 0, stream, a); break;
+                    case 7: hipLaunchKernelGGL(fir_fft_dma_nt_kernel<7>, dim3(grid), dim3(kFftNT), 0, stream, a); break;
+#endif
+                    default: hipLaunchKernelGGL(fir_fft_dma_kernel, dim3(grid), dim3(kFftNT), 0, stream, a); break;
+                }
+            }
             else if (a.real2) hipLaunchKernelGGL((fir_fft_kernel<1, false, true>), dim3(grid), dim3(kFftNT), 0, stream, a);
             else if (r) hipLaunchKernelGGL((fir_fft_kernel<1, true>), dim3(grid), dim3(kFftNT), 0, stream, a);
             else hipLaunchKernelGGL((fir_fft_kernel<1, false>), dim3(grid), dim3(kFftNT), 0, stream, a);

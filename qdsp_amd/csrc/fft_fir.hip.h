@@ -59,7 +59,9 @@ struct FftArgs {
     int m_shift;              // fir_fft1k_kernel, strided: log2(decm) when decm is a power of two <= 64 (a lane keeps all or none of its 16 elements), else -1
     int abl;                  // diagnostic builds of fir_fft_dmapk_kernel: ablation mask (0: the product)
     unsigned* stamps;         // diagnostic build of fir_fft_dmapk_kernel only: [grid][kFftStampWords] per-phase tick sums + timeline (nullptr: off)
-    int nt;                   // fir_fft_dmapk_kernel: bit 0 = non-temporal DMA of the rows no neighbour re-reads, bit 1 = non-temporal stores
+    int nt;                   // the LDS-DMA kernels (both; a template parameter of each): bit 0 = non-temporal DMA of rows 1-14 of an interior segment
+                              // (rows 0 and 15 hold the overlap a neighbour reads as well), bit 1 = non-temporal 16-byte stores.  QDSP_HIP_FFT_NT, or by
+                              // the overlap: 3 up to 256, 2 above, 0 where segments do not start on 64-byte boundaries (launch_fft, qdsp_hip.hip)
     int dma;                  // 1: fir_fft_dma_kernel (FIR<complex_t>, 16-byte aligned in / out, overlap <= 2048): segments arrive by LDS-DMA
     int real2;                // 1: real samples (4-byte in/out/hist); block b = real segments 2b (re) and 2b+1 (im)
     // NCO (rot only).  x[j] exp(j phi(j)) filtered by h == exp(j phi(p - (N-1))) * (x filtered by

@@ -1055,7 +1055,13 @@ int launch_fft(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d
     // (grouped only when the groups fill the chip -- measured crossover ~1000 groups, 2^25 samples at decimation 8 --
     // below that the segments run one per workgroup: a 1e6-sample block 10 us instead of 28)
     // FIR<complex_t> on aligned buffers: the LDS-DMA form (fir_fft_dma_kernel, fft_fir.hip)
-    a.nt = qk::knob(qk::K_FFT_NT, 0);
+    // The sample stream's cache policy in the LDS-DMA kernels (FftArgs::nt), by the overlap, as measured at 2^27 samples
+    // (profiles/r06_fir256_taps.txt): non-temporal stores pay where every segment starts on a 64-byte boundary (overlap a multiple of 8
+    // samples: - 2.1 % at 1000 taps, - 4.8 % at 57; 0 % at an overlap of 60, + 1.2 % at 62), the non-temporal DMA beside them only while
+    // the two rows that stay cacheable hold the whole overlap (- 4.5 ... - 6.6 % up to 256; + 1.1 % at 2048).  QDSP_HIP_FFT_NT overrides.
+    // (Buffers that are themselves not 64-byte aligned put the segments where an overlap of 62 puts them: plain accesses.)
+    const bool on_64_bytes = a.ov % 8 == 0 && ((((uintptr_t)d_in) | ((uintptr_t)d_out)) & 63) == 0;
+    a.nt = qk::knob(qk::K_FFT_NT, !on_64_bytes ? 0 : a.ov <= 256 ? 3 : 2);
     a.abl = qk::knob(qk::K_FFT_ABL, 0);
     a.stamps = reinterpret_cast<unsigned*>(qk::knobs_snapshot()->fft_stamps);   // diagnostic: scripts/stamp_fir_fft.py
     a.dma = (a.dec == 1 && !a.strided && !a.rot && e->ch == 2 && a.vec && a.ov <= 2048) ? qk::knob(qk::K_FFT_DMA, 1) : 0;   // 1: scalar arithmetic, 2: packed
