@@ -584,6 +584,61 @@ int qdsp_hip_costas_process_batch_dev(void* h, const void* d_in, int64_t count, 
 int qdsp_hip_costas_reset(void* h);
 void qdsp_hip_costas_destroy(void* h);
 
+/* ---- symbol timing : MMClockRecovery<float | complex_t>, src/dsp/clock_recovery.h:68-243 ------ */
+/* The Mueller & Mueller clock recovery of PSKDemod (complex_t rows) and MSKDemod (float rows); kind 0 = float, 1 = complex_t;
+ * nchan channel-major rows per call, strides in samples, each channel with its own omega, gains, limit and state, all on the
+ * device.  Per row the symbols are a function of the concatenated input, whatever the call cuts.  With x[p] the row's samples
+ * numbered from the last reset (x[p] = 0 for p < 0), mu = 0.5, dynOmega = omega and pos = 0 at the start, while pos lies inside
+ * the samples received so far:
+ *   idx = (int)roundf(mu * 128.0f);  y = sum_{k = 0..7} x[pos - 7 + k] taps[idx][k]: every product in FP64 (exact), added in tap
+ *        order in FP64, rounded to float once; per component for complex rows.  y is the next symbol of the row.
+ *   e = the phase error of the row's type (clock_recovery.h:152-153 / :157-176), in float, every operation rounded on its own;
+ *        clamped to +-1.
+ *   dynOmega = clamp(dynOmega + gainOmega e, omegaMin, omegaMax);  mu += dynOmega + muGain e;  pos += floorf(mu);  mu -= floorf(mu).
+ * The reference leaves the order of the eight-term sum to VOLK; here it is fixed as stated, so outputs, counts and state do not
+ * depend, bit for bit, on the call cuts, the row's place in the batch, strides, alignment or the entry point.
+ * The table: 129 rows of 8 taps, the MMSE interpolator for a band of +-0.25 cycles per sample, computed by the library: row m
+ * (mu = m / 128) solves R h = p, R[k][l] = sinc((k - l) / 2), p[k] = sinc((3 + mu - k) / 2), sinc(x) = sin(pi x) / (pi x), in
+ * FP64; an entry below 1e-9 in magnitude is 0, every other is rounded to six significant decimal digits and then to float
+ * (get_interp_taps).  It agrees with the reference's table to 5e-7; set_interp_taps loads any finite table instead, the
+ * reference's own for instance, for all channels of the handle.
+ * Parameter rule (create, set_omega, set_gains, set_limit; else QDSP_HIP_EINVAL): all values finite, omega > 0, 0 <= rel_limit < 1,
+ * and with omegaMin = omega - omega rel_limit, omegaMax = omega + omega rel_limit in float: omegaMin - |mu_gain| >= 1 (every step
+ * is at least one sample) and omegaMax + |mu_gain| < 2^20.  Hence a call of `count` samples emits at most
+ * out_size(count) = ceil(count / floor(min over channels of (omegaMin - |mu_gain|))) <= count symbols per row.
+ * Departures from the reference: its cap of 2 omega count outputs per call cannot bind under the rule and is absent; the delay
+ * line is zero after create / reset (the reference's is uninitialised); any count >= 0 is served (the reference copies out of
+ * range below 7); its clamp of a negative position is unreachable; set_omega forms the limits from the new omega (the reference's
+ * setOmega from the old one) and, like it, restarts dynOmega at omega.  A NaN phase error: the symbol just formed is written, then
+ * the row stops -- it emits nothing further and its mu reads back NaN -- until reset or set_state; other rows are not affected.
+ * set_* / get_state / set_state / reset / set_interp_taps synchronise the device and act from the next call; chan -1 = every
+ * channel.  get_state: mu, dynOmega and next = pos - samples received (>= 0).  set_state: 0 <= mu < 1, dynOmega finite,
+ * 0 <= next <= 2^21; detector and delay line are kept.
+ * process_batch_dev: asynchronous; out_stride >= out_size(count); d_in != d_out, spans may not overlap; device pointers aligned
+ * to the sample (4 / 8 bytes); a row's symbols go to its first slots, the per-row counts to d_counts (int32[nchan], may be NULL)
+ * and to the handle (get_counts: the last call's, synchronising).  process_dev: the rows back to back (strides count and
+ * out_size(count)).  process / process_ex (nchan 1) return the symbol count; link codes as for every *_process_ex, but the
+ * output link is QDSP_HIP_LINK_HOST or _DEVICE only (the count must be known on return: anything else is QDSP_HIP_EINVAL);
+ * `count` <= max_block where a side is on the host (else QDSP_HIP_ESIZE). */
+int qdsp_hip_mmcr_create(void** h, int device, int kind, int nchan, int max_block, float omega, float gain_omega, float mu_gain,
+                         float rel_limit);
+int qdsp_hip_mmcr_set_omega(void* h, int chan, float omega);
+int qdsp_hip_mmcr_set_gains(void* h, int chan, float gain_omega, float mu_gain);
+int qdsp_hip_mmcr_set_limit(void* h, int chan, float rel_limit);
+int qdsp_hip_mmcr_get_state(void* h, int chan, float* mu, float* dyn_omega, int* next);
+int qdsp_hip_mmcr_set_state(void* h, int chan, float mu, float dyn_omega, int next);
+int64_t qdsp_hip_mmcr_out_size(void* h, int64_t count);
+int qdsp_hip_mmcr_get_interp_taps(void* h, float* taps);
+int qdsp_hip_mmcr_set_interp_taps(void* h, const float* taps);
+int qdsp_hip_mmcr_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_mmcr_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_mmcr_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_mmcr_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
+                                    int* d_counts, void* hip_stream);
+int qdsp_hip_mmcr_get_counts(void* h, int* counts);
+int qdsp_hip_mmcr_reset(void* h);
+void qdsp_hip_mmcr_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

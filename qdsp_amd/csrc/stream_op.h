@@ -1,4 +1,4 @@
-// stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas .hip):
+// stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr .hip):
 // the head of the handle, its creation and release, and the one block-graph path (*_process_ex) and timing loop behind all of
 // them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
@@ -28,6 +28,7 @@ constexpr uint32_t kStereoFmMagic = 0x5153464du;  // "QSFM"  stereo_fm.hip.h
 constexpr uint32_t kFfAgcMagic = 0x51464147u;     // "QFAG"  ff_agc.hip.h
 constexpr uint32_t kCagcMagic = 0x51434147u;      // "QCAG"  cagc.hip.h
 constexpr uint32_t kCostasMagic = 0x51434f53u;    // "QCOS"  costas.hip.h
+constexpr uint32_t kMmcrMagic = 0x514d4d43u;      // "QMMC"  mmcr.hip.h
 constexpr int kDemodMaxChan = 65535;              // grid.y
 
 // The head of every per-row handle.  No virtual functions: every as_* reads `magic` at offset 0 of a handle of unknown kind.
@@ -58,7 +59,7 @@ int64_t launch_as(StreamOp* op, const void* d_in, int64_t count, int64_t in_stri
     return F(static_cast<T*>(op), d_in, count, in_stride, d_out, out_stride, s);
 }
 
-// h if it is one of the seven kinds above
+// h if it is one of the kinds above
 StreamOp* as_stream_op(void* h);
 
 // The argument checks every create begins with, after the operator's own: QDSP_HIP_EINVAL (h, nchan, max_block), then

@@ -1140,3 +1140,122 @@ class CostasLoop(_Level):
 
 
 __all__ += ["CostasLoop"]
+
+
+class MmClockRecovery(_RowOp):
+    """dsp::MMClockRecovery<T> (src/dsp/clock_recovery.h:68-243): Mueller & Mueller symbol timing.  Every symbol is the 8-tap MMSE
+    interpolation of the input at the loop's position (129 fractional steps, the table in `interp_taps()`), and the type's phase
+    error of the symbol moves the symbol period (`gain_omega`, within omega (1 +- rel_limit)) and the position (`mu_gain`).
+    `kind_or_dtype`: 0 / "real" / float32 for float rows (MSKDemod), 1 / "complex" / complex64 for complex_t rows (PSKDemod).
+    One row per lane, 16 rows to a wave (include/qdsp_hip.h: symbol timing); `nchan` rows per launch, each with its own parameters
+    (scalars or one value per channel) and state.  A call of n samples emits a data-dependent number of symbols per row, at most
+    `out_size(n)`: `process` returns them (one row), `process_batch` the padded rows and the counts."""
+
+    _prefix = "qdsp_hip_mmcr"
+    REAL, COMPLEX = 0, 1
+
+    def __init__(self, kind_or_dtype, omega, gain_omega=0.01 * 0.01 / 4, mu_gain=0.01, rel_limit=0.005, nchan: int = 1,
+                 device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        self.kind = FeedForwardAgc._kind_of(kind_or_dtype)
+        self._np, self._tt = (np.complex64, "complex64") if self.kind == self.COMPLEX else (np.float32, "float32")
+        par = [np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,)) for v in (omega, gain_omega, mu_gain, rel_limit)]
+        capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, max_block, *(float(v[0]) for v in par)),
+                   "qdsp_hip_mmcr_create")
+        if any(np.any(v != v[0]) for v in par):
+            for c in range(self.nchan):
+                # (one at a time a change may leave the rule for a moment: gains and limit that fit every omega first)
+                self.set_gains(0.0, 0.0, c)
+                self.set_limit(0.0, c)
+                self.set_omega(float(par[0][c]), c)
+                self.set_limit(float(par[3][c]), c)
+                self.set_gains(float(par[1][c]), float(par[2][c]), c)
+
+    def set_omega(self, omega: float, chan: int = -1):
+        """Samples per symbol; also restarts the loop's period there.  Takes effect from the next call."""
+        capi.check(self._fn("set_omega")(self._h, int(chan), omega), "qdsp_hip_mmcr_set_omega")
+
+    def set_gains(self, gain_omega: float, mu_gain: float, chan: int = -1):
+        capi.check(self._fn("set_gains")(self._h, int(chan), gain_omega, mu_gain), "qdsp_hip_mmcr_set_gains")
+
+    def set_limit(self, rel_limit: float, chan: int = -1):
+        capi.check(self._fn("set_limit")(self._h, int(chan), rel_limit), "qdsp_hip_mmcr_set_limit")
+
+    def get_state(self, chan: int = 0):
+        """(mu, dynOmega, next): next = samples from the end of the input so far to the next symbol (synchronises the device)."""
+        mu, dyn, nx = C.c_float(), C.c_float(), C.c_int()
+        capi.check(self._fn("get_state")(self._h, int(chan), C.byref(mu), C.byref(dyn), C.byref(nx)))
+        return float(mu.value), float(dyn.value), int(nx.value)
+
+    def set_state(self, mu: float, dyn_omega: float, next: int, chan: int = -1):
+        capi.check(self._fn("set_state")(self._h, int(chan), float(mu), float(dyn_omega), int(next)), "qdsp_hip_mmcr_set_state")
+
+    def out_size(self, n: int) -> int:
+        """The most symbols per row a call of `n` samples can emit: the slots an output row needs."""
+        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), "qdsp_hip_mmcr_out_size"))
+
+    def interp_taps(self) -> np.ndarray:
+        t = np.zeros((129, 8), dtype=np.float32)
+        capi.check(self._fn("get_interp_taps")(self._h, t.ctypes.data_as(C.POINTER(C.c_float))))
+        return t
+
+    def set_interp_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        assert t.shape == (129, 8), t.shape
+        capi.check(self._fn("set_interp_taps")(self._h, t.ctypes.data_as(C.POINTER(C.c_float))), "qdsp_hip_mmcr_set_interp_taps")
+
+    def counts(self) -> np.ndarray:
+        """The symbols per row of the last call (synchronises the device)."""
+        c = np.zeros(self.nchan, dtype=np.int32)
+        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
+        return c
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=self._np)
+        assert a.ndim == 1, a.shape
+        y = np.empty(max(self.out_size(a.size), 1), dtype=self._np)
+        no = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:no]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
+        n = x.numel()
+        if out is None:
+            out = torch.empty(max(self.out_size(n), 1), dtype=dt, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= self.out_size(n)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
+        return out[:int(self.counts()[0])]
+
+    def process_batch(self, x, out=None, count: int = None, counts=None):
+        """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count).  Returns (rows, counts): the
+        (nchan, out_size(count)) view of `out`, row c's symbols in its first counts[c] slots and the rest untouched, and the
+        counts as an int32 device tensor (`counts`, or a new one).  Asynchronous; `out` may not overlap `x`."""
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        no = self.out_size(n)
+        if out is None:
+            out = torch.empty((self.nchan, max(no, 1)), dtype=dt, device=x.device)
+        if counts is None:
+            counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
+        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= no and out.stride(1) == 1
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), counts.data_ptr(), stream)
+        capi.check(int(rc), self._prefix + "_process_batch_dev")
+        return out[:, :no], counts
+
+
+__all__ += ["MmClockRecovery"]
