@@ -1071,10 +1071,14 @@ int launch_fft(Engine* e, const void* d_in, int64_t count, int64_t nout, void* d
     const int units = grouped ? (a.nblocks + a.dec - 1) / a.dec : a.nblocks;
     int nwg = 256 * per_cu;
     if (nwg > units) nwg = units;
+    // (QDSP_HIP_FFT_WG_PER_CU below 1: one workgroup walks every unit, as in launch_pfb and launch_rm -- a grid of none would leave the
+    // segment loop a stride of 0.  A call with no unit at all keeps its grid of the hand-over workgroup alone.)
+    if (nwg < 1 && units > 0) nwg = 1;
     a.n_long = nwg;   // (n_long, rounds: read by the LDS-DMA kernels only)
     a.rounds = (units + nwg - 1) / (nwg > 0 ? nwg : 1);
     if (a.dma) {   // tapered grid (fft_fir.hip.h): the resident workgroups (four per CU) are long, short ones follow
-        const int slots = 256 * qk::knob(qk::K_FFT_WG_PER_CU, 4);
+        const int slots_per_cu = qk::knob(qk::K_FFT_WG_PER_CU, 4);
+        const int slots = 256 * (slots_per_cu < 1 ? 1 : slots_per_cu);   // (below 1 reads as 1: fft_taper_rounds divides by the slots)
         a.n_long = a.nblocks < slots ? a.nblocks : slots;
         a.rounds = qk::fft_taper_rounds(a.nblocks, slots);
         nwg = a.n_long + qk::fft_taper_short_count(a.nblocks, slots, a.rounds);
