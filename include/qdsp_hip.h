@@ -639,6 +639,115 @@ int qdsp_hip_mmcr_get_counts(void* h, int* counts);
 int qdsp_hip_mmcr_reset(void* h);
 void qdsp_hip_mmcr_destroy(void* h);
 
+/* ---- FIR over channel rows : FIR<float | complex_t>, src/dsp/filter.h:51-74, batched -------- */
+/* qdsp_hip_fir_cf32 / _f32 over nchan channel-major rows in one launch; kind 0 = float rows, 1 = complex_t rows; strides in
+ * samples; real taps, one tap count per handle (1 <= ntaps <= 4096), every channel with its own tap values and its own history
+ * (the last ntaps - 1 inputs of the row, 0 after create / reset), all on the device:
+ *     y[c][i] = sum_k taps[c][k] x[c][i - (ntaps - 1) + k]
+ * Every output component is the FP32 chain acc = fmaf(taps[c][k], x, acc) for k = 0 .. ntaps - 1 from +0.0f (row_fir_kernel): its
+ * bits depend on the row's taps and the ntaps samples under them alone -- not on the call cuts, the row's place in the batch,
+ * strides, alignment or the entry point -- and are those of qdsp_hip_fir_cf32 / _f32 in QDSP_HIP_FIR_DIRECT mode.  No zero taps
+ * are padded in: a NaN at sample p reaches outputs p .. p + ntaps - 1 of its row and nothing else.
+ * create loads the same taps into every channel.  set_taps: chan -1 = every channel, and ntaps may change, the history kept
+ * and resized as qdsp_hip_fir_cf32_set_taps does (the newest samples preserved); chan >= 0 = that channel, ntaps must equal the
+ * current count (else QDSP_HIP_EINVAL).  get_history / set_history: the ntaps - 1 samples of one channel, oldest first.
+ * set_taps / get_history / set_history / reset synchronise the device and act from the next call.
+ * process_batch_dev: asynchronous; device pointers aligned to the sample (4 / 8 bytes); 16-byte aligned output rows take the vector
+ * stores.  d_in == d_out or spans that overlap are QDSP_HIP_EINVAL (a tile reads its neighbours' inputs).  count == 0 launches
+ * nothing and keeps the history.  process_dev: the rows back to back.  process / process_ex (nchan 1): as for every
+ * *_process_ex, `count` <= max_block where a side is on the host (else QDSP_HIP_ESIZE).
+ * tile: the outputs per workgroup of row_fir_kernel; tap_group: the taps per unrolled group of its tap loop (what a test needs to
+ * place its sizes around the kernel's boundaries). */
+int qdsp_hip_rowfir_create(void** h, int device, int kind, int nchan, const float* taps, int ntaps, int max_block);
+int qdsp_hip_rowfir_set_taps(void* h, int chan, const float* taps, int ntaps);
+int qdsp_hip_rowfir_ntaps(void* h);
+int qdsp_hip_rowfir_get_history(void* h, int chan, float* hist);
+int qdsp_hip_rowfir_set_history(void* h, int chan, const float* hist);
+int qdsp_hip_rowfir_process(void* h, const float* in, int count, float* out);
+int qdsp_hip_rowfir_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_rowfir_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_rowfir_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
+                                      void* hip_stream);
+int qdsp_hip_rowfir_reset(void* h);
+void qdsp_hip_rowfir_destroy(void* h);
+int qdsp_hip_rowfir_tile(void);
+int qdsp_hip_rowfir_tap_group(void);
+
+/* ---- DelayImag : src/dsp/processing.h:300-344 ------------------------------------------------ */
+/* The one-sample Q delay of offset PSK over nchan complex_t rows: out[i] = {in[i].re, in[i - 1].im}, in[-1].im = the row's carried
+ * lastIm (0 after create / reset; get_state / set_state, chan -1 = every channel).  Bit copies only (delay_imag_kernel): NaN
+ * payloads and signed zeros pass unchanged.  Pointers 8-byte aligned; d_in == d_out or overlapping spans are QDSP_HIP_EINVAL (the
+ * reference's loop may run in place; here a lane reads its neighbour's sample); count == 0 keeps the state.  Entry points as
+ * for qdsp_hip_rowfir_*. */
+int qdsp_hip_delay_imag_create(void** h, int device, int nchan, int max_block);
+int qdsp_hip_delay_imag_get_state(void* h, int chan, float* last_im);
+int qdsp_hip_delay_imag_set_state(void* h, int chan, float last_im);
+int qdsp_hip_delay_imag_process(void* h, const float* in_iq, int count, float* out_iq);
+int qdsp_hip_delay_imag_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_delay_imag_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_delay_imag_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out,
+                                          int64_t out_stride, void* hip_stream);
+int qdsp_hip_delay_imag_reset(void* h);
+void qdsp_hip_delay_imag_destroy(void* h);
+
+/* ---- PSKDemod<ORDER, OFFSET> and MSKDemod : src/dsp/demodulator.h:499-682 -------------------- */
+/* A whole demodulator chain over nchan complex_t rows in one call, every intermediate on the device.  A chain handle owns one
+ * handle of each stage and runs their *_process_batch_dev on the call's stream, one after the other:
+ *   PSK (order 2 / 4 / 8, offset 0 / 1):  qdsp_hip_cagc (set point 1.0f, max gain 65535, agc_rate: PSKDemod::init) ->
+ *        qdsp_hip_rowfir kind 1 (rrc_taps, the same for every channel until set) -> qdsp_hip_costas of that order, in place ->
+ *        qdsp_hip_delay_imag (offset chains only) -> qdsp_hip_mmcr kind 1.  Symbols: complex_t.
+ *   MSK:  qdsp_hip_demod QDSP_HIP_DEMOD_FM (sample_rate, deviation) -> qdsp_hip_mmcr kind 0.  Symbols: float.
+ * so the symbols, counts and state are, bit for bit, those of the separate handles called in that order.  The parameters are
+ * each stage's own and are checked by it (create returns the stage's error and leaves nothing allocated).
+ * stage(which, &s): the BORROWED handle of a stage -- QDSP_HIP_PSK_AGC / _RRC / _COSTAS / _DELAY / _CLOCK, QDSP_HIP_MSK_FM / _CLOCK;
+ * _DELAY on a chain without offset is QDSP_HIP_EINVAL.  Every per-channel setter and getter goes through it (qdsp_hip_cagc_set,
+ * qdsp_hip_rowfir_set_taps, qdsp_hip_costas_set_bandwidth, qdsp_hip_mmcr_set_omega, ... and each stage's state).  A borrowed handle
+ * is never processed on and never destroyed: it belongs to the chain and dies with it.
+ * tap_dev(which, &rows, &stride): the device rows stage `which` wrote in the last call, `*stride` samples apart, 16-byte aligned,
+ * valid until the next call on this handle; read them on that call's stream.  The intermediates share two scratch row sets, so
+ * only rows that no later stage has overwritten are there: _COSTAS, _DELAY, _AGC of a chain without offset, and _FM; *rows is NULL
+ * for _RRC (the Costas loop runs in place over them), for _AGC of an offset chain (the delay stage reuses them) and before the
+ * first call; _CLOCK (its rows are the caller's) and _DELAY without offset are QDSP_HIP_EINVAL.
+ * out_size(count) = the clock stage's qdsp_hip_mmcr_out_size, asked at call time.  process_batch_dev: asynchronous; d_in rows
+ * 8-byte aligned, in_stride >= count; d_out, out_stride and d_counts as for qdsp_hip_mmcr_process_batch_dev.  count == 0 moves no
+ * stage's state and clears the counts.  process_dev: the rows back to back (strides count and out_size(count)).  process /
+ * process_ex (nchan 1) return the symbol count; the output link is QDSP_HIP_LINK_HOST or _DEVICE only, as for qdsp_hip_mmcr.
+ * The scratch rows grow to the largest call seen (a call larger than max_block and every call before it synchronises the device
+ * once).  reset resets every stage.  get_counts synchronises the device.  qdsp_hip_last_kernel reports the clock stage's launch. */
+#define QDSP_HIP_PSK_AGC 0
+#define QDSP_HIP_PSK_RRC 1
+#define QDSP_HIP_PSK_COSTAS 2
+#define QDSP_HIP_PSK_DELAY 3
+#define QDSP_HIP_PSK_CLOCK 4
+#define QDSP_HIP_MSK_FM 0
+#define QDSP_HIP_MSK_CLOCK 1
+int qdsp_hip_psk_create(void** h, int device, int order, int offset, int nchan, int max_block, const float* rrc_taps, int ntaps,
+                        float agc_rate, float costas_bw, float omega, float gain_omega, float mu_gain, float rel_limit);
+int qdsp_hip_psk_stage(void* h, int which, void** stage);
+int qdsp_hip_psk_tap_dev(void* h, int which, void** d_rows, int64_t* stride);
+int64_t qdsp_hip_psk_out_size(void* h, int64_t count);
+int qdsp_hip_psk_process(void* h, const float* in_iq, int count, float* out_iq);
+int qdsp_hip_psk_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_psk_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_psk_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
+                                   int* d_counts, void* hip_stream);
+int qdsp_hip_psk_get_counts(void* h, int* counts);
+int qdsp_hip_psk_reset(void* h);
+void qdsp_hip_psk_destroy(void* h);
+int qdsp_hip_msk_create(void** h, int device, int nchan, int max_block, float sample_rate, float deviation, float omega,
+                        float gain_omega, float mu_gain, float rel_limit);
+int qdsp_hip_msk_stage(void* h, int which, void** stage);
+int qdsp_hip_msk_tap_dev(void* h, int which, void** d_rows, int64_t* stride);
+int64_t qdsp_hip_msk_out_size(void* h, int64_t count);
+int qdsp_hip_msk_process(void* h, const float* in_iq, int count, float* out);
+int qdsp_hip_msk_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_msk_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_msk_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
+                                   int* d_counts, void* hip_stream);
+int qdsp_hip_msk_get_counts(void* h, int* counts);
+int qdsp_hip_msk_reset(void* h);
+void qdsp_hip_msk_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

@@ -278,6 +278,39 @@ def load():
     sig(p + "_get_counts", i32, vp, C.POINTER(i32))
     sig(p + "_reset", i32, vp)
     sig(p + "_destroy", None, vp)
+    p = "qdsp_hip_rowfir"
+    sig(p + "_create", i32, pvp, i32, i32, i32, fp, i32, i32)
+    sig(p + "_set_taps", i32, vp, i32, fp, i32)
+    sig(p + "_ntaps", i32, vp)
+    sig(p + "_get_history", i32, vp, i32, vp)
+    sig(p + "_set_history", i32, vp, i32, vp)
+    sig(p + "_tile", i32)
+    sig(p + "_tap_group", i32)
+    p = "qdsp_hip_delay_imag"
+    sig(p + "_create", i32, pvp, i32, i32, i32)
+    sig(p + "_get_state", i32, vp, i32, fp)
+    sig(p + "_set_state", i32, vp, i32, C.c_float)
+    for p in ("qdsp_hip_rowfir", "qdsp_hip_delay_imag"):
+        sig(p + "_process", i32, vp, vp, i32, vp)
+        sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+        sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+        sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp)
+        sig(p + "_reset", i32, vp)
+        sig(p + "_destroy", None, vp)
+    f32 = C.c_float
+    sig("qdsp_hip_psk_create", i32, pvp, i32, i32, i32, i32, i32, fp, i32, f32, f32, f32, f32, f32, f32)
+    sig("qdsp_hip_msk_create", i32, pvp, i32, i32, i32, f32, f32, f32, f32, f32, f32)
+    for p in ("qdsp_hip_psk", "qdsp_hip_msk"):
+        sig(p + "_stage", i32, vp, i32, pvp)
+        sig(p + "_tap_dev", i32, vp, i32, pvp, C.POINTER(i64))
+        sig(p + "_out_size", i64, vp, i64)
+        sig(p + "_process", i32, vp, vp, i32, vp)
+        sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+        sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+        sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, i64, vp, vp)
+        sig(p + "_get_counts", i32, vp, C.POINTER(i32))
+        sig(p + "_reset", i32, vp)
+        sig(p + "_destroy", None, vp)
     sig("qdsp_hip_set_done_event", i32, vp, vp)
     sig("qdsp_hip_event_create", i32, i32, pvp)
     sig("qdsp_hip_event_destroy", i32, vp)

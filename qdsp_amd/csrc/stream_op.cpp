@@ -77,7 +77,7 @@ StreamOp* as_stream_op(void* h) {
     if (!d) return nullptr;
     switch (d->magic) {
         case kDemodMagic: case kDeempMagic: case kLevelMagic: case kStereoFmMagic: case kFfAgcMagic: case kCagcMagic: case kCostasMagic:
-        case kMmcrMagic:
+        case kMmcrMagic: case kRowFirMagic: case kDelayImagMagic: case kChainMagic:
             return d;
     }
     return nullptr;

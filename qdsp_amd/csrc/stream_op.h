@@ -1,4 +1,5 @@
-// stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr .hip):
+// stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr /
+// rowfir .hip, psk_chain.cpp):
 // the head of the handle, its creation and release, and the one block-graph path (*_process_ex) and timing loop behind all of
 // them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
@@ -29,6 +30,9 @@ constexpr uint32_t kFfAgcMagic = 0x51464147u;     // "QFAG"  ff_agc.hip.h
 constexpr uint32_t kCagcMagic = 0x51434147u;      // "QCAG"  cagc.hip.h
 constexpr uint32_t kCostasMagic = 0x51434f53u;    // "QCOS"  costas.hip.h
 constexpr uint32_t kMmcrMagic = 0x514d4d43u;      // "QMMC"  mmcr.hip.h
+constexpr uint32_t kRowFirMagic = 0x51524649u;    // "QRFI"  rowfir.hip.h
+constexpr uint32_t kDelayImagMagic = 0x5144494du; // "QDIM"  rowfir.hip.h
+constexpr uint32_t kChainMagic = 0x5150534bu;     // "QPSK"  psk_chain.cpp (PSKDemod and MSKDemod chains)
 constexpr int kDemodMaxChan = 65535;              // grid.y
 
 // The head of every per-row handle.  No virtual functions: every as_* reads `magic` at offset 0 of a handle of unknown kind.

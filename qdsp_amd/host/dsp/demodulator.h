@@ -10,9 +10,9 @@
 //   AMDemod                 qdsp_hip_demod_* (AM): |x| minus the mean of the call, the mean summed in FP64
 //   SSBDemod                qdsp_hip_ssb_cf32_*: the xlator's NCO with the reference's phaseDelta, real part out
 // StereoFMDemod is in dsp/stereo_demod.h: the reference's block has no PLL -- FloatFMDemod, a FIR<float> on the 19 kHz pilot, AGC
-// and three element-wise lines -- and is one handle here (qdsp_hip_stereo_fm_*).  The blocks of the reference header built around
-// serial loops (MSKDemod, PSKDemod) are not provided; their parts are: ComplexAGC (dsp/processing.h), FIR (dsp/filter.h), CostasLoop
-// (dsp/pll.h), MMClockRecovery (dsp/clock_recovery.h).
+// and three element-wise lines -- and is one handle here (qdsp_hip_stereo_fm_*).  MSKDemod and PSKDemod are in dsp/psk_demod.h, one
+// chain handle each; their parts as blocks of their own: ComplexAGC (dsp/processing.h), FIR (dsp/filter.h), CostasLoop (dsp/pll.h),
+// DelayImag (dsp/psk_demod.h), MMClockRecovery (dsp/clock_recovery.h).
 #pragma once
 #include <cmath>
 

@@ -1,5 +1,5 @@
 // dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch, dsp::AGC, dsp::FeedForwardAGC<T> and dsp::ComplexAGC, HIP-backed
-// (the reference's other blocks in this header -- DelayImag, packer ... -- are not provided).
+// (DelayImag is in dsp/psk_demod.h; the reference's other blocks in this header -- packer ... -- are not provided).
 //
 // Drop-in for src/dsp/processing.h:10-81.  init()/setSampleRate()/setFrequency() compute
 // phaseDelta exactly as the reference does -- theta = (freq/sampleRate) * 2.0f * FL_M_PI in

@@ -1259,3 +1259,316 @@ class MmClockRecovery(_RowOp):
 
 
 __all__ += ["MmClockRecovery"]
+
+
+class RowFir(_Level):
+    """dsp::FIR<T> (src/dsp/filter.h:51-74) over `nchan` channel rows in one launch (include/qdsp_hip.h: FIR over channel rows):
+    y[c][i] = sum_k taps[c][k] x[c][i - (T - 1) + k], every output component the chain acc = fmaf(taps[k], x, acc) in tap order --
+    the bits of `Fir(...).set_mode(Fir.DIRECT)` row by row.  `kind_or_dtype` as for MmClockRecovery (float32 or complex64 rows);
+    `taps`: one row for all channels or an (nchan, T) array.  Entry points by input as for Squelch and Agc; `out` may not overlap
+    the input.  TILE: the kernel's outputs per workgroup; TAP_GROUP: the taps per unrolled group of its tap loop."""
+
+    _prefix = "qdsp_hip_rowfir"
+    REAL, COMPLEX = 0, 1
+
+    def __init__(self, kind_or_dtype, taps, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        self.kind = FeedForwardAgc._kind_of(kind_or_dtype)
+        self._set_kind()
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        first, p = _taps_ptr(t if t.ndim == 1 else t[0])
+        capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, p, len(first), max_block), "qdsp_hip_rowfir_create")
+        if t.ndim == 2:
+            assert t.shape[0] == self.nchan, t.shape
+            for c in range(1, self.nchan):
+                self.set_taps(t[c], c)
+
+    def _set_kind(self):
+        self._np, self._tt = (np.complex64, "complex64") if self.kind == self.COMPLEX else (np.float32, "float32")
+
+    @classmethod
+    def tile(cls) -> int:
+        return int(capi.load().qdsp_hip_rowfir_tile())
+
+    @classmethod
+    def tap_group(cls) -> int:
+        return int(capi.load().qdsp_hip_rowfir_tap_group())
+
+    @property
+    def ntaps(self) -> int:
+        return capi.check(self._fn("ntaps")(self._h))
+
+    def set_taps(self, taps, chan: int = -1):
+        """chan -1: every channel, and the count may change (the history keeps its newest samples); chan >= 0: the same count."""
+        t, p = _taps_ptr(taps)
+        capi.check(self._fn("set_taps")(self._h, int(chan), p, len(t)), "qdsp_hip_rowfir_set_taps")
+
+    def get_history(self, chan: int = 0) -> np.ndarray:
+        n = self.ntaps - 1
+        a = np.zeros(max(n, 1), dtype=self._np)
+        capi.check(self._fn("get_history")(self._h, int(chan), a.ctypes.data))
+        return a[:n]
+
+    def set_history(self, hist, chan: int = 0):
+        a = np.ascontiguousarray(hist, dtype=self._np)
+        assert a.size == self.ntaps - 1, (a.size, self.ntaps)
+        capi.check(self._fn("set_history")(self._h, int(chan), a.ctypes.data))
+
+
+class DelayImag(_Level):
+    """dsp::DelayImag (src/dsp/processing.h:300-344), the one-sample Q delay of offset PSK: out[i] = {x[i].re, x[i - 1].im}, bit
+    copies, over `nchan` complex64 rows.  Entry points by input as for Squelch and Agc; `out` may not overlap the input."""
+
+    _prefix = "qdsp_hip_delay_imag"
+    _np, _tt = np.complex64, "complex64"
+
+    def __init__(self, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_delay_imag_create")
+
+    def get_state(self, chan: int = 0) -> np.float32:
+        """The carried lastIm, as the float32 it is (synchronises the device)."""
+        v = C.c_float()
+        capi.check(self._fn("get_state")(self._h, int(chan), C.byref(v)))
+        return np.float32(v.value)
+
+    def set_state(self, last_im: float, chan: int = -1):
+        capi.check(self._fn("set_state")(self._h, int(chan), float(last_im)))
+
+
+def rrc_taps(count: int, sample_rate: float, baud_rate: float, alpha: float) -> np.ndarray:
+    """The taps FIR<complex_t> gets from dsp::RRCTaps (src/dsp/window.h:161-225): `count | 1` taps computed and normalised, the
+    first `count` of them used.  Every step in the reference's types and order, as the C++ mirror's dsp/window.h computes it."""
+    import math
+
+    f32 = np.float32
+    n = int(count) | 1
+    centre = n // 2
+    pi, a = float(FL_M_PI), f32(alpha)
+    sps = float(f32(sample_rate) / f32(baud_rate))
+    a4, om, op = float(f32(4) * a), float(f32(1) - a), float(f32(1) + a)
+    taps, total = np.zeros(n, f32), 0.0
+    for i in range(n):
+        t = float(i - centre)
+        arg = pi * t / sps
+        edge = a4 * t / sps
+        q = edge * edge - 1
+        if abs(q) >= 0.000001:
+            tail = math.sin(om * arg) / (a4 * t / sps) if i != centre else float(f32(f32(om) * FL_M_PI) / f32(a4))
+            v = a4 * (math.cos(op * arg) + tail) / (q * pi)
+        elif a == 1:
+            v = -1.0
+        else:
+            lo, hi = om * arg, op * arg
+            num = (math.sin(hi) * op * pi - math.cos(lo) * (float(f32(om) * FL_M_PI) * sps) / (a4 * t)
+                   + math.sin(lo) * sps * sps / (a4 * t * t))
+            v = a4 * num / (float(f32(f32(f32(-32) * FL_M_PI) * a) * a) * t / sps)
+        taps[i] = f32(v)
+        total += float(taps[i])
+    for i in range(n):
+        taps[i] = f32(float(taps[i]) / total)
+    return taps[:int(count)].copy()
+
+
+def _borrowed(cls, handle, **attrs):
+    """A non-owning view of a stage handle of a chain with `cls`'s methods: closing it does nothing."""
+    view = type("Borrowed" + cls.__name__, (cls,), {"close": lambda self: None})
+    v = view.__new__(view)
+    _Op.__init__(v)
+    v._h = C.c_void_p(handle)
+    for k, val in attrs.items():
+        setattr(v, k, val)
+    return v
+
+
+class _Chain(_RowOp):
+    """What PskDemod and MskDemod share: a chain handle (include/qdsp_hip.h: PSKDemod and MSKDemod) runs every stage over `nchan`
+    rows in one call with the intermediates on the device.  numpy input: the host entry point (one channel), returning the
+    symbols; a 1-D tensor: *_process_dev; a 2-D one: `process_batch`, returning (rows, counts)."""
+
+    _sym_np, _sym_tt = np.complex64, "complex64"
+
+    def stage(self, which: int):
+        """A non-owning view of stage `which` with that operator's methods (setters, getters, state); never process on it."""
+        p = C.c_void_p()
+        capi.check(self._fn("stage")(self._h, int(which), C.byref(p)), self._prefix + "_stage")
+        return self._view(int(which), p.value)
+
+    def tap(self, which: int, count: int = None):
+        """The rows stage `which` wrote in the last call, as a (nchan, count) device tensor view (None where a later stage has
+        overwritten them); valid until the next call."""
+        import torch
+
+        p, st = C.c_void_p(), C.c_int64()
+        capi.check(self._fn("tap_dev")(self._h, int(which), C.byref(p), C.byref(st)), self._prefix + "_tap_dev")
+        if not p.value:
+            return None
+        cplx = self._tap_complex(int(which))
+        nfloat = self.nchan * st.value * (2 if cplx else 1)
+
+        class _Holder:
+            pass
+
+        holder = _Holder()
+        holder.__cuda_array_interface__ = {"shape": (nfloat,), "typestr": "<f4", "data": (p.value, False), "version": 2}
+        t = torch.as_tensor(holder, device=f"cuda:{self.device}")
+        t = torch.view_as_complex(t.view(self.nchan, st.value, 2)) if cplx else t.view(self.nchan, st.value)
+        return t if count is None else t[:, :int(count)]
+
+    def out_size(self, n: int) -> int:
+        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), self._prefix + "_out_size"))
+
+    def counts(self) -> np.ndarray:
+        """The symbols per row of the last call (synchronises the device)."""
+        c = np.zeros(self.nchan, dtype=np.int32)
+        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
+        return c
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=np.complex64)
+        assert a.ndim == 1, a.shape
+        y = np.empty(max(self.out_size(a.size), 1), dtype=self._sym_np)
+        no = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:no]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        dt = getattr(torch, self._sym_tt)
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.complex64 and x.dim() == 1 and self.nchan == 1, "one contiguous row"
+        n = x.numel()
+        if out is None:
+            out = torch.empty(max(self.out_size(n), 1), dtype=dt, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= self.out_size(n)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
+        return out[:int(self.counts()[0])]
+
+    def process_batch(self, x, out=None, count: int = None, counts=None):
+        """Channel c = row c of the 2-D complex64 tensor `x` (rows may be padded).  Returns (rows, counts) as
+        MmClockRecovery.process_batch does.  Asynchronous."""
+        import torch
+
+        dt = getattr(torch, self._sym_tt)
+        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.complex64 and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        no = self.out_size(n)
+        if out is None:
+            out = torch.empty((self.nchan, max(no, 1)), dtype=dt, device=x.device)
+        if counts is None:
+            counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
+        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= no and out.stride(1) == 1
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), counts.data_ptr(), stream)
+        capi.check(int(rc), self._prefix + "_process_batch_dev")
+        return out[:, :no], counts
+
+    def _set_clock(self, clock, omega, gain_omega, mu_gain, rel_limit):
+        par = [np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,)) for v in (omega, gain_omega, mu_gain, rel_limit)]
+        if any(np.any(v != v[0]) for v in par):
+            for c in range(self.nchan):   # (the order of MmClockRecovery.__init__: no step leaves the parameter rule)
+                clock.set_gains(0.0, 0.0, c)
+                clock.set_limit(0.0, c)
+                clock.set_omega(float(par[0][c]), c)
+                clock.set_limit(float(par[3][c]), c)
+                clock.set_gains(float(par[1][c]), float(par[2][c]), c)
+
+
+class PskDemod(_Chain):
+    """dsp::PSKDemod<ORDER, OFFSET> (src/dsp/demodulator.h:566-682): ComplexAgc (set point 1, max gain 65535) -> RowFir with the
+    RRC taps -> CostasLoop of `order` -> DelayImag (`offset`) -> MmClockRecovery, over `nchan` complex64 rows in one call.
+    Parameters are scalars or one value per channel.  The taps are `rrc_taps(rrc_tap_count, sample_rate, baud_rate, rrc_alpha)`
+    per channel, the symbol period sample_rate / baud_rate in float.  `stage(PskDemod.AGC / RRC / COSTAS / DELAY / CLOCK)` gives
+    the stage's own methods; `tap(which)` the rows it wrote in the last call."""
+
+    _prefix = "qdsp_hip_psk"
+    AGC, RRC, COSTAS, DELAY, CLOCK = 0, 1, 2, 3, 4
+
+    def __init__(self, order: int, offset: bool, sample_rate, baud_rate, rrc_tap_count: int = 32, rrc_alpha=0.32, agc_rate=10e-4,
+                 costas_bw=0.004, omega_gain=0.01 * 0.01 / 4, mu_gain=0.01, omega_rel_limit=0.005, nchan: int = 1, device: int = 0,
+                 max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        self.order, self.offset = int(order), bool(offset)
+        b = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,))   # noqa: E731
+        sr, baud, alpha, rate, bw = b(sample_rate), b(baud_rate), b(rrc_alpha), b(agc_rate), b(costas_bw)
+        taps = [rrc_taps(rrc_tap_count, sr[c], baud[c], alpha[c]) for c in range(self.nchan)]
+        omega = (sr / baud).astype(np.float32)
+        _, p = _taps_ptr(taps[0])
+        go, gm, rl = b(omega_gain), b(mu_gain), b(omega_rel_limit)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.order, int(self.offset), self.nchan, max_block, p, len(taps[0]),
+                                      float(rate[0]), float(bw[0]), float(omega[0]), float(go[0]), float(gm[0]), float(rl[0])),
+                   "qdsp_hip_psk_create")
+        rrc, agc, costas = self.stage(self.RRC), self.stage(self.AGC), self.stage(self.COSTAS)
+        for c in range(1, self.nchan):
+            if not np.array_equal(taps[c], taps[0]):
+                rrc.set_taps(taps[c], c)
+            if rate[c] != rate[0]:
+                agc.set(1.0, 65535.0, float(rate[c]), c)
+            if bw[c] != bw[0]:
+                costas.set_bandwidth(float(bw[c]), c)
+        self._set_clock(self.stage(self.CLOCK), omega, go, gm, rl)
+
+    def _tap_complex(self, which: int) -> bool:
+        return True
+
+    def _view(self, which: int, handle):
+        if which == self.AGC:
+            return _borrowed(ComplexAgc, handle, nchan=self.nchan, device=self.device)
+        if which == self.RRC:
+            v = _borrowed(RowFir, handle, nchan=self.nchan, device=self.device, kind=RowFir.COMPLEX)
+            v._set_kind()
+            return v
+        if which == self.COSTAS:
+            return _borrowed(CostasLoop, handle, nchan=self.nchan, device=self.device, order=self.order)
+        if which == self.DELAY:
+            return _borrowed(DelayImag, handle, nchan=self.nchan, device=self.device)
+        return _borrowed(MmClockRecovery, handle, nchan=self.nchan, device=self.device, kind=1, _np=np.complex64, _tt="complex64")
+
+
+class MskDemod(_Chain):
+    """dsp::MSKDemod (src/dsp/demodulator.h:499-564): FmDemod (mono) -> MmClockRecovery on float rows, over `nchan` complex64 rows
+    in one call; the symbols are float32.  Parameters are scalars or one value per channel.  The three loop parameters are
+    forwarded (the reference's constructor drops them).  `stage(MskDemod.FM / CLOCK)`, `tap(MskDemod.FM)`."""
+
+    _prefix = "qdsp_hip_msk"
+    _sym_np, _sym_tt = np.float32, "float32"
+    FM, CLOCK = 0, 1
+
+    def __init__(self, sample_rate, deviation, baud_rate, omega_gain=0.01 * 0.01 / 4, mu_gain=0.01, omega_rel_limit=0.005,
+                 nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        b = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,))   # noqa: E731
+        sr, dev, baud = b(sample_rate), b(deviation), b(baud_rate)
+        omega = (sr / baud).astype(np.float32)
+        go, gm, rl = b(omega_gain), b(mu_gain), b(omega_rel_limit)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block, float(sr[0]), float(dev[0]), float(omega[0]),
+                                      float(go[0]), float(gm[0]), float(rl[0])), "qdsp_hip_msk_create")
+        fm = self.stage(self.FM)
+        for c in range(1, self.nchan):
+            if sr[c] != sr[0] or dev[c] != dev[0]:
+                fm.set_fm(float(sr[c]), float(dev[c]), c)
+        self._set_clock(self.stage(self.CLOCK), omega, go, gm, rl)
+
+    def _tap_complex(self, which: int) -> bool:
+        return False
+
+    def _view(self, which: int, handle):
+        if which == self.FM:
+            return _borrowed(FmDemod, handle, nchan=self.nchan, device=self.device)
+        return _borrowed(MmClockRecovery, handle, nchan=self.nchan, device=self.device, kind=0, _np=np.float32, _tt="float32")
+
+
+__all__ += ["RowFir", "DelayImag", "PskDemod", "MskDemod", "rrc_taps"]
