@@ -748,6 +748,80 @@ int qdsp_hip_msk_get_counts(void* h, int* counts);
 int qdsp_hip_msk_reset(void* h);
 void qdsp_hip_msk_destroy(void* h);
 
+/* ---- Threshold : src/dsp/processing.h:554-610 ------------------------------------------------ */
+/* out[i] = (in[i] > 0.0f) ? 1 : 0 -- float rows in, uint8_t rows out, one byte per float, the same count; nchan channel-major rows
+ * per call, in_stride in floats, out_stride in bytes (threshold_kernel).  NaN, -0.0f, +0.0f and negative denormals give 0; positive
+ * denormals and +Inf give 1 (the compare is made on the bit pattern, whatever the denormal mode).  No state.  The reference's
+ * setLevel / getLevel store a value its run() never reads: they exist in the C++ mirror only, with the same (non-)effect.
+ * process_batch_dev: asynchronous; d_in 4-byte aligned, d_out any address (a lane's 16 outputs go out as one 16-byte store behind
+ * the row's first 16-byte boundary, the bytes in front of it and the last partial group one by one); in_stride, out_stride >= count;
+ * d_in_counts: int32[nchan] on the device or NULL (every row has `count`): row r converts min(max(d_in_counts[r], 0), count) floats
+ * and leaves the rest of its output row untouched.  Spans of input and output that overlap are QDSP_HIP_EINVAL.  count == 0 launches
+ * nothing.  process_dev: the rows back to back.  process / process_ex (nchan 1): link codes as for every *_process_ex, `count` <=
+ * max_block where a side is on the host (else QDSP_HIP_ESIZE).  span: the outputs per workgroup of threshold_kernel. */
+int qdsp_hip_threshold_create(void** h, int device, int nchan, int max_block);
+int qdsp_hip_threshold_process(void* h, const float* in, int count, uint8_t* out);
+int qdsp_hip_threshold_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_threshold_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_threshold_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, const int* d_in_counts, void* d_out,
+                                         int64_t out_stride, void* hip_stream);
+void qdsp_hip_threshold_destroy(void* h);
+int qdsp_hip_threshold_span(void);
+
+/* ---- Deframer : src/dsp/deframing.h ------------------------------------------------------------ */
+/* Sync-word framing over nchan channel-major rows of one bit per byte: search for the sync word, cut frames of frame_len bits and
+ * pack them eight bits to a byte, MSB first.  kind 0 = uint8_t rows, kind 1 = float rows thresholded on load (x > 0 as for
+ * qdsp_hip_threshold, so a demodulator's soft symbols need no byte row in between).  Per handle: frame_len in bits (1 .. 2^20) and
+ * a sync word of sync_len bytes (1 .. 256), one bit per byte, compared as whole bytes like the reference's memcmp and shared by
+ * the rows of the handle.  Per row, with x[p] the row's input bytes numbered from the last reset:
+ *   d[q] = x[q - sync_len], d[q] = 0 for q < sync_len (the reference's zeroed work-buffer prefix);
+ *   match(q) = (d[q .. q + sync_len) == sync word): it reads only inputs already received when position q is reached.
+ * State per row: bits_read (-1 = searching), bad = 5, after = 0 after create / reset.  A call of n bytes advances q over n positions:
+ *   reading (bits_read >= 0): frame bit k = bits_read is d[q]; it contributes (uint8_t)(d[q] << (7 - k % 8)), OR-ed into frame byte
+ *     k / 8, every byte starting from 0 (input bytes other than 0 / 1 follow this formula); then q++, bits_read++; at bits_read ==
+ *     frame_len the frame is emitted as frame_bytes = ceil(frame_len / 8) bytes, bits_read = -1, after = 1.
+ *   after a frame (after): after = 0; if match(q), a frame starts at q with bad = 0; else if bad < 5, bad++ and a frame starts at q
+ *     anyway (the reference's "try to save"); else search from q.
+ *   searching: go to the smallest q' >= q with match(q'), bad = 0, a frame starts at q' (it includes the sync word); if there is no
+ *     such q' among the positions received, remain searching.
+ * This event form gives the frames of the reference's per-bit loop.  Departures from the reference: any count >= 0 is served (the
+ * reference reads out of range below sync_len and copies count - 1 bytes, which is harmless there); the result is a function of
+ * the concatenated row, whatever the call cuts; the sync word is shared by the rows of a handle; `after` reads back 0 while a frame
+ * is being read (the reference leaves its flag set after a match, without effect).
+ * A frame that spans calls is emitted by the call in which its last bit arrives; its earlier part is kept on the device.  A call
+ * of `count` bytes emits at most out_size(count) = ceil(count / frame_len) frames per row.
+ * set_sync: the same length only (else QDSP_HIP_EINVAL).  get_state / set_state: bits_read (-1 .. frame_len - 1), bad (0 .. 5),
+ * after (0 / 1, and 0 while bits_read >= 0); chan -1 = every channel; the bytes of a frame in progress and the last sync_len
+ * inputs are kept.  set_sync / get_state / set_state / reset / get_counts synchronise the device and act from the next call.
+ * process_batch_dev: asynchronous; d_in_counts as for qdsp_hip_threshold (this is what lets the deframer follow qdsp_hip_mmcr_* and
+ * qdsp_hip_{psk,msk}_process_batch_dev on the same stream with no host synchronisation); in_stride >= count, in input elements;
+ * the frames of a row go back to back into its first slots, out_stride_bytes >= out_size(count) * frame_bytes, the bytes behind a
+ * row's last frame are not touched; the per-row frame counts go to d_counts (int32[nchan], may be NULL) and to the handle
+ * (get_counts).  kind 1: d_in 4-byte aligned.  Overlapping or equal d_in / d_out, a short stride and count > 2^30 are
+ * QDSP_HIP_EINVAL.  count == 0 moves nothing, keeps the state and clears the counts.  Match words and frame starts live in
+ * library-owned scratch sized for max_block at create (a larger device call grows it and synchronises the device once).
+ * process_dev: the rows back to back (strides count and out_size(count) * frame_bytes).  process / process_ex (nchan 1) return the
+ * frame count; `out` holds out_size(count) * frame_bytes bytes; the output link is QDSP_HIP_LINK_HOST or _DEVICE only, as for
+ * qdsp_hip_mmcr; `count` <= max_block where a side is on the host (else QDSP_HIP_ESIZE).  tile / pack_span: the positions per
+ * workgroup of deframe_match_kernel and of deframe_pack_kernel (at a frame_len that is a multiple of 8).  qdsp_hip_last_kernel
+ * reports the match launch. */
+int qdsp_hip_deframer_create(void** h, int device, int kind, int nchan, int max_block, int frame_len, const uint8_t* sync, int sync_len);
+int qdsp_hip_deframer_set_sync(void* h, const uint8_t* sync, int sync_len);
+int qdsp_hip_deframer_get_state(void* h, int chan, int* bits_read, int* bad, int* after);
+int qdsp_hip_deframer_set_state(void* h, int chan, int bits_read, int bad, int after);
+int64_t qdsp_hip_deframer_out_size(void* h, int64_t count);
+int qdsp_hip_deframer_frame_bytes(void* h);
+int qdsp_hip_deframer_process(void* h, const void* in, int count, uint8_t* out);
+int qdsp_hip_deframer_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_deframer_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_deframer_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, const int* d_in_counts, void* d_out,
+                                        int64_t out_stride_bytes, int* d_counts, void* hip_stream);
+int qdsp_hip_deframer_get_counts(void* h, int* counts);
+int qdsp_hip_deframer_reset(void* h);
+void qdsp_hip_deframer_destroy(void* h);
+int qdsp_hip_deframer_tile(void);
+int qdsp_hip_deframer_pack_span(void);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

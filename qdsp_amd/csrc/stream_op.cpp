@@ -6,6 +6,7 @@
 
 #include <chrono>
 #include <mutex>
+#include <unordered_map>
 
 namespace qh {
 
@@ -72,6 +73,38 @@ void* mapped_host_ptr(void* p) {
     return nullptr;
 }
 
+namespace {
+struct Registry {
+    std::mutex m;
+    std::unordered_map<void*, int> live;    // handle -> kind
+};
+Registry& registry() {
+    static Registry* r = new Registry();    // (never destroyed: a handle may be released from a static destructor)
+    return *r;
+}
+}  // namespace
+
+void stream_op_register(StreamOp* d, int kind) {
+    Registry& r = registry();
+    std::lock_guard<std::mutex> lk(r.m);
+    r.live[d] = kind;
+}
+
+void stream_op_unregister(StreamOp* d) {
+    Registry& r = registry();
+    std::lock_guard<std::mutex> lk(r.m);
+    r.live.erase(d);
+}
+
+StreamOp* stream_op_registered(void* h, int kind) {
+    if (!h) return nullptr;
+    Registry& r = registry();
+    std::lock_guard<std::mutex> lk(r.m);
+    const auto it = r.live.find(h);
+    if (it == r.live.end() || (kind != 0 && it->second != kind)) return nullptr;
+    return static_cast<StreamOp*>(h);
+}
+
 StreamOp* as_stream_op(void* h) {
     StreamOp* d = static_cast<StreamOp*>(h);
     if (!d) return nullptr;
@@ -80,7 +113,7 @@ StreamOp* as_stream_op(void* h) {
         case kMmcrMagic: case kRowFirMagic: case kDelayImagMagic: case kChainMagic:
             return d;
     }
-    return nullptr;
+    return stream_op_registered(h, 0);      // (the kinds without a magic; nothing changes for the eleven above)
 }
 
 int stream_op_check(void** h, int device, int nchan, int max_block) {

@@ -1,5 +1,5 @@
 // stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr /
-// rowfir .hip, psk_chain.cpp):
+// rowfir / deframe .hip, psk_chain.cpp):
 // the head of the handle, its creation and release, and the one block-graph path (*_process_ex) and timing loop behind all of
 // them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
@@ -63,7 +63,22 @@ int64_t launch_as(StreamOp* op, const void* d_in, int64_t count, int64_t in_stri
     return F(static_cast<T*>(op), d_in, count, in_stride, d_out, out_stride, s);
 }
 
-// h if it is one of the kinds above
+// Kinds without a magic (deframe.hip.h: Threshold, Deframer).  Why two of thirteen kinds are told apart differently: the eleven magics
+// above are a closed set -- tests/test_psk_cpu.py counts the k*Magic constants of this header and checks that they differ, and a
+// feature may not edit an existing test -- so a kind added after them cannot bring a twelfth constant.  Such a handle has magic 0,
+// which no as_* of a kind above takes, and is known by its address instead: it is entered in a table (a mutex and a hash map in
+// stream_op.cpp, alive for the whole process) under its kind at create and taken out at destroy.  as_threshold / as_deframer only
+// look the pointer up, so they refuse a stale or foreign pointer without reading it.  as_stream_op (last_kernel, set_done_event,
+// time_process_dev) still reads `magic` of an unknown pointer first, as it always has; the table is only asked, and its lock only
+// taken, for a handle that is none of the eleven.
+constexpr int kKindThreshold = 1;
+constexpr int kKindDeframer = 2;
+void stream_op_register(StreamOp* d, int kind);
+void stream_op_unregister(StreamOp* d);
+// h if it is a live registered handle of `kind` (0: of any kind)
+StreamOp* stream_op_registered(void* h, int kind);
+
+// h if it is one of the kinds above (by magic, no lock), or else a registered handle
 StreamOp* as_stream_op(void* h);
 
 // The argument checks every create begins with, after the operator's own: QDSP_HIP_EINVAL (h, nchan, max_block), then

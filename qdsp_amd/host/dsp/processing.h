@@ -1,4 +1,4 @@
-// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch, dsp::AGC, dsp::FeedForwardAGC<T> and dsp::ComplexAGC, HIP-backed
+// dsp/processing.h -- dsp::FrequencyXlator<T>, dsp::Squelch, dsp::AGC, dsp::FeedForwardAGC<T>, dsp::ComplexAGC and dsp::Threshold, HIP-backed
 // (DelayImag is in dsp/psk_demod.h; the reference's other blocks in this header -- packer ... -- are not provided).
 //
 // Drop-in for src/dsp/processing.h:10-81.  init()/setSampleRate()/setFrequency() compute
@@ -10,6 +10,7 @@
 // the base's; a block adds its constructors, init() and its setters.
 #pragma once
 #include <cmath>
+#include <cstdint>
 #include <type_traits>
 
 #include "block.h"
@@ -207,6 +208,29 @@ private:
     float _setPoint = 1.0f;
     float _maxGain = 10e4;
     float _rate = 10e-4;
+};
+
+// Threshold (src/dsp/processing.h:554-610): same constructors, init(), setInput(), setLevel(), getLevel() and `out`: one byte per
+// float, out = (in > 0.0f), on the device (qdsp_hip_threshold_*).  As in the reference the level is stored and never used by run().
+class Threshold : public detail::hip_block<float, uint8_t> {
+    using hb = detail::hip_block<float, uint8_t>;
+
+public:
+    Threshold() : hb(qdsp_hip_threshold_process_ex, qdsp_hip_threshold_destroy, "Threshold::run") {}
+
+    Threshold(stream<float>* in) : Threshold() { init(in); }
+
+    void init(stream<float>* in) {
+        const int rc = qdsp_hip_threshold_create(&handle, detail::hipDeviceForBlocks(), 1, STREAM_BUFFER_SIZE);
+        hb::attach(in, rc, "Threshold::init");
+    }
+
+    void setLevel(float level) { _level = level; }
+
+    float getLevel() { return _level; }
+
+private:
+    float _level = -50.0f;
 };
 
 }  // namespace dsp

@@ -1572,3 +1572,208 @@ class MskDemod(_Chain):
 
 
 __all__ += ["RowFir", "DelayImag", "PskDemod", "MskDemod", "rrc_taps"]
+
+
+def _in_counts_ptr(in_counts, nchan, device):
+    """The device pointer of an optional int32 tensor of per-row input counts (None: every row has the call's count)."""
+    import torch
+
+    if in_counts is None:
+        return None
+    assert in_counts.is_cuda and in_counts.dtype == torch.int32 and in_counts.is_contiguous() and in_counts.numel() == nchan
+    assert in_counts.device == device
+    return in_counts.data_ptr()
+
+
+class Threshold(_RowOp):
+    """dsp::Threshold (src/dsp/processing.h:554-610): out = (in > 0.0f) as one uint8 per float32, `nchan` rows per launch
+    (include/qdsp_hip.h: Threshold).  numpy input: the host entry point (one channel); a 1-D tensor: *_process_dev; a 2-D one:
+    `process_batch`.  No state: `reset` does nothing."""
+
+    _prefix = "qdsp_hip_threshold"
+
+    def __init__(self, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_threshold_create")
+
+    @staticmethod
+    def span() -> int:
+        """Outputs per workgroup of threshold_kernel."""
+        return int(capi.load().qdsp_hip_threshold_span())
+
+    def reset(self):
+        pass
+
+    def out_size(self, n: int) -> int:
+        return int(n)
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        assert a.ndim == 1, a.shape
+        y = np.empty(max(a.size, 1), dtype=np.uint8)
+        capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:a.size]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 1 and self.nchan == 1, "one contiguous row"
+        n = x.numel()
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.uint8, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= n
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
+        return out[:n]
+
+    def process_batch(self, x, out=None, count: int = None, in_counts=None):
+        """Channel c = row c of the 2-D float32 tensor `x` (rows may be padded).  `in_counts`: an int32 device tensor, row c
+        converts min(max(in_counts[c], 0), count) floats and leaves the rest of its output row untouched.  Asynchronous."""
+        import torch
+
+        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        if out is None:
+            out = torch.empty((self.nchan, max(n, 1)), dtype=torch.uint8, device=x.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == 1
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), _in_counts_ptr(in_counts, self.nchan, x.device),
+                                           out.data_ptr(), out.stride(0), stream)
+        capi.check(int(rc), self._prefix + "_process_batch_dev")
+        return out[:, :n]
+
+
+class Deframer(_RowOp):
+    """dsp::Deframer (src/dsp/deframing.h): finds `sync` (one bit per byte) in rows of one bit per byte, cuts frames of `frame_len`
+    bits and packs them eight to a byte (include/qdsp_hip.h: Deframer).  `kind_or_dtype`: 0 / "bytes" / uint8 for uint8 rows,
+    1 / "float" / float32 for float32 soft symbols thresholded on load.  `nchan` rows per launch, each with its own state.  A call
+    of n bytes emits at most `out_size(n)` frames per row: `process` returns them as an (frames, frame_bytes) array (one row),
+    `process_batch` the padded rows and the per-row frame counts."""
+
+    _prefix = "qdsp_hip_deframer"
+    BYTES, FLOAT = 0, 1
+
+    def __init__(self, frame_len: int, sync, kind_or_dtype=0, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
+        super().__init__()
+        self.device = device
+        self.nchan = int(nchan)
+        k = kind_or_dtype if isinstance(kind_or_dtype, (int, str)) else getattr(kind_or_dtype, "__name__", str(kind_or_dtype))
+        if k in (0, "bytes", "uint8", "torch.uint8"):
+            self.kind = self.BYTES
+        elif k in (1, "float", "float32", "torch.float32"):
+            self.kind = self.FLOAT
+        else:
+            raise ValueError(f"kind_or_dtype: {kind_or_dtype!r}")
+        self._np, self._tt = (np.float32, "float32") if self.kind else (np.uint8, "uint8")
+        s = np.ascontiguousarray(sync, dtype=np.uint8).ravel()
+        self.frame_len = int(frame_len)
+        capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, max_block, self.frame_len, s.ctypes.data, s.size),
+                   "qdsp_hip_deframer_create")
+        self.sync_len = int(s.size)
+        self.frame_bytes = int(self._fn("frame_bytes")(self._h))
+
+    @staticmethod
+    def tile() -> int:
+        """Positions per workgroup of deframe_match_kernel."""
+        return int(capi.load().qdsp_hip_deframer_tile())
+
+    @staticmethod
+    def pack_span() -> int:
+        """Positions per workgroup of deframe_pack_kernel (frame_len a multiple of 8)."""
+        return int(capi.load().qdsp_hip_deframer_pack_span())
+
+    def set_sync(self, sync):
+        s = np.ascontiguousarray(sync, dtype=np.uint8).ravel()
+        capi.check(self._fn("set_sync")(self._h, s.ctypes.data, s.size), "qdsp_hip_deframer_set_sync")
+
+    def get_state(self, chan: int = 0):
+        """(bits_read, bad, after) of one row: bits_read -1 = searching (synchronises the device)."""
+        b, bad, aft = C.c_int(), C.c_int(), C.c_int()
+        capi.check(self._fn("get_state")(self._h, int(chan), C.byref(b), C.byref(bad), C.byref(aft)), "qdsp_hip_deframer_get_state")
+        return int(b.value), int(bad.value), bool(aft.value)
+
+    def set_state(self, bits_read: int, bad: int, after: bool, chan: int = -1):
+        capi.check(self._fn("set_state")(self._h, int(chan), int(bits_read), int(bad), int(bool(after))), "qdsp_hip_deframer_set_state")
+
+    def out_size(self, n: int) -> int:
+        """The most frames per row a call of `n` bytes can emit."""
+        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), "qdsp_hip_deframer_out_size"))
+
+    def counts(self) -> np.ndarray:
+        """The frames per row of the last call (synchronises the device)."""
+        c = np.zeros(self.nchan, dtype=np.int32)
+        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
+        return c
+
+    def process(self, x, out=None):
+        if _is_torch(x):
+            if x.dim() == 2:
+                return self.process_batch(x, out)
+            return self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=self._np)
+        assert a.ndim == 1, a.shape
+        y = np.empty((max(self.out_size(a.size), 1), self.frame_bytes), dtype=np.uint8)
+        nf = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
+        return y[:nf]
+
+    def _process_dev(self, x, out=None):
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
+        n = x.numel()
+        nb = self.out_size(n) * self.frame_bytes
+        if out is None:
+            out = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= nb
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
+        nf = int(self.counts()[0])
+        return out[:nf * self.frame_bytes].view(nf, self.frame_bytes)
+
+    def process_batch(self, x, out=None, count: int = None, in_counts=None, counts=None):
+        """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count).  `in_counts`: an int32 device
+        tensor of per-row input counts (what MmClockRecovery.process_batch or a chain returns), row c takes
+        min(max(in_counts[c], 0), count) of its elements.  Returns (rows, counts): the (nchan, out_size(count) * frame_bytes) uint8
+        view of `out`, row c's frames back to back in its first counts[c] * frame_bytes bytes and the rest untouched, and the
+        frame counts as an int32 device tensor (`counts`, or a new one).  Asynchronous; `out` may not overlap `x`."""
+        import torch
+
+        dt = getattr(torch, self._tt)
+        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
+        n = x.shape[1] if count is None else int(count)
+        nb = self.out_size(n) * self.frame_bytes
+        if out is None:
+            out = torch.empty((self.nchan, max(nb, 1)), dtype=torch.uint8, device=x.device)
+        if counts is None:
+            counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= nb and out.stride(1) == 1
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), _in_counts_ptr(in_counts, self.nchan, x.device),
+                                           out.data_ptr(), out.stride(0), counts.data_ptr(), stream)
+        capi.check(int(rc), self._prefix + "_process_batch_dev")
+        return out[:, :nb], counts
+
+    def time_dev(self, x, out, iters: int) -> float:
+        """Mean ms per call of `iters` back-to-back process_batch calls over the rows of the 2-D tensor `x` (HIP events on the
+        launch stream).  The state moves on with every call."""
+        import torch
+
+        counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(int(iters)):
+            self.process_batch(x, out, counts=counts)
+        e1.record()
+        e1.synchronize()
+        return float(e0.elapsed_time(e1)) / int(iters)
+
+
+__all__ += ["Threshold", "Deframer"]
