@@ -448,53 +448,145 @@ class Math:
 
 
 
-class _Demod(_Op):
-    """Complex in, real out (one float per sample, or a stereo_t {l, r} pair: `_stereo`).  numpy input: the host entry
-    point (one channel); a 1-D torch tensor: *_process_dev; a 2-D one: one row per channel (`process_batch`)."""
+def _per_chan(v, nchan: int) -> np.ndarray:
+    """A scalar, or one value per channel, as `nchan` floats."""
+    return np.broadcast_to(np.asarray(v, dtype=np.float32), (nchan,))
 
-    _stereo = False
-    nchan = 1
 
-    def _out_shape(self, *lead):
-        return (*lead, 2) if self._stereo else tuple(lead)
+_REAL_COMPLEX = (("real", "float32"), ("complex", "complex64"))
+
+
+def _parse_kind(k, kinds, what: str, exact: bool = False) -> int:
+    """The kind a `kind_or_dtype` argument spells: its index in `kinds`, one (word, dtype name) per kind.  By default any int passes
+    through for the library to judge, and a numpy or torch dtype or scalar type is known by the dtype name in the last dotted part
+    of its str.  `exact` (Deframer): the index, the word, or the dtype's name, bare or as torch prints it, and nothing else."""
+    if exact:
+        name = k if isinstance(k, (int, str)) else getattr(k, "__name__", str(k))
+    elif isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+        return int(k)
+    else:
+        name = str(k).rsplit(".", 1)[-1]
+    for kind, (word, dt) in enumerate(kinds):
+        if (name in (kind, word, dt, "torch." + dt)) if exact else ((isinstance(k, str) and k == word) or dt in name):
+            return kind
+    raise ValueError(f"{what}: {' or '.join(dt for _, dt in kinds)} rows, not {k!r}")
+
+
+def _row_type(kind: int):
+    """The numpy sample type of a REAL / COMPLEX kind's rows."""
+    return np.complex64 if kind == 1 else np.float32
+
+
+def _tail(width: int) -> tuple:
+    """The trailing shape of samples `width` elements wide: stereo_t pairs sit in a last dimension of 2."""
+    return (2,) if width == 2 else ()
+
+
+def _in_counts_ptr(in_counts, nchan, device):
+    """The device pointer of an optional int32 tensor of per-row input counts (None: every row has the call's count)."""
+    import torch
+
+    if in_counts is None:
+        return None
+    assert in_counts.is_cuda and in_counts.dtype == torch.int32 and in_counts.is_contiguous() and in_counts.numel() == nchan
+    assert in_counts.device == device
+    return in_counts.data_ptr()
+
+
+class _Rows(_Op):
+    """An operator over `nchan` channel rows and its three entry forms.  numpy input: the host entry point (one channel); a tensor of
+    one row: *_process_dev on torch's current stream; a tensor of `nchan` rows: `process_batch`.  A class states what is its own:
+
+        _np, _out_np      the numpy type of an input / output sample; the torch dtype has the same name (_out_np None: as the input)
+        _iw, _ow          2 where a sample is a stereo_t pair, a trailing dimension of 2; else 1.  Also the unit of the row stride.
+        _emits            the outputs of a call of n samples: "n"; "returned" (_OutSize): at most out_size(n), the call returns the
+                          count; "counts" (_Counts): out_size(n) slots per row and a count per row
+        _per              the elements of one output (a Deframer's frame: frame_bytes)
+        _takes_in_counts  the batch entry point takes an int32 tensor of per-row input counts
+        _flat             the 1-D form reads `nchan` rows back to back (the demodulators); every other class refuses nchan > 1 there
+        _batch_fn         the batch entry point's name, where it is not <prefix>_process_batch_dev"""
+
+    _np, _out_np = np.float32, None
+    _iw = _ow = 1
+    _emits = "n"
+    _per = 1
+    _takes_in_counts = False
+    _flat = False
+    _batch_fn = None
+
+    def _torch_types(self):
+        import torch
+
+        return torch, getattr(torch, np.dtype(self._np).name), getattr(torch, np.dtype(self._out_np or self._np).name)
+
+    def _slots(self, n: int) -> int:
+        """The elements an output row needs for a call of `n` samples."""
+        return (n if self._emits == "n" else self.out_size(n)) * self._per
+
+    def _result(self, y):
+        """The 1-D result as the class shows it (Deframer: frames by bytes)."""
+        return y
 
     def process(self, x, out=None):
         if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=np.complex64)
-        y = np.empty(self._out_shape(max(a.size, 1)), dtype=np.float32)
-        capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:a.size]
+            return self.process_batch(x, out) if x.dim() == 1 + self._iw else self._process_dev(x, out)
+        a = np.ascontiguousarray(x, dtype=self._np)
+        assert self._flat or (a.ndim == self._iw and a.shape[1:] == _tail(self._iw)), a.shape
+        n = a.size // self._iw
+        y = np.empty((max(self._slots(n), 1),) + _tail(self._ow), dtype=self._out_np or self._np)
+        rc = capi.check(self._fn("process")(self._h, a.ctypes.data, n, y.ctypes.data), self._prefix + "_process")
+        return self._result(y[:(n if self._emits == "n" else rc) * self._per])
 
     def _process_dev(self, x, out=None):
-        import torch
-
-        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.complex64
-        n = x.numel() // self.nchan
+        torch, idt, odt = self._torch_types()
+        assert x.is_cuda and x.is_contiguous() and x.dtype == idt, "one contiguous row"
+        assert self._flat or (self.nchan == 1 and x.dim() == self._iw and tuple(x.shape[1:]) == _tail(self._iw)), "one contiguous row"
+        n = x.numel() // self._iw // self.nchan
+        assert n * self._iw * self.nchan == x.numel(), "whole rows"
+        assert out is None or (out.is_cuda and out.is_contiguous() and out.dtype == odt and out.dim() == self._ow and tuple(out.shape[1:]) == _tail(self._ow))
+        cap = self._slots(n) * self.nchan
         if out is None:
-            out = torch.empty(self._out_shape(max(x.numel(), 1)), dtype=torch.float32, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= x.numel()
+            out = torch.empty((max(cap, 1),) + _tail(self._ow), dtype=odt, device=x.device)
+        assert out.shape[0] >= cap
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
-        return out[:x.numel()]
+        rc = capi.check(int(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream)), self._prefix + "_process_dev")
+        if self._emits == "n":
+            no = n * self.nchan
+        else:
+            no = rc if self._emits == "returned" else int(self.counts()[0])
+        return self._result(out[:no * self._per])
 
     def process_batch(self, x, out=None, count: int = None):
-        """Channel c = row c of the 2-D complex64 tensor `x` (rows may be padded: x.stride(0) >= count, e.g. the
-        Channelizer's output, or a slice of it).  Returns (nchan, count) float32 (stereo: (nchan, count, 2))."""
-        import torch
+        """Channel c = row c of the tensor `x`, (nchan, n) or, of stereo_t samples, (nchan, n, 2).  Rows may be padded (x.stride(0)
+        beyond the row: another operator's batch output, or a slice of it) and `count` may stop short of them.  Returns the
+        (nchan, outputs) view of `out`, or of new rows.  out=x works in place unless the class says that they may not overlap."""
+        return self._batch(x, out, count)
 
-        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.complex64 and x.shape[0] == self.nchan and x.stride(1) == 1
+    def _batch(self, x, out, count, in_counts=None, counts=None):
+        torch, idt, odt = self._torch_types()
+        iw, ow = self._iw, self._ow
+        assert x.is_cuda and x.dtype == idt and x.dim() == 1 + iw and x.shape[0] == self.nchan and x.stride(1) == iw and x.stride(0) % iw == 0
+        assert iw == 1 or (x.shape[2] == 2 and x.stride(2) == 1)
         n = x.shape[1] if count is None else int(count)
+        cap = self._slots(n)
         if out is None:
-            out = torch.empty(self._out_shape(self.nchan, max(n, 1)), dtype=torch.float32, device=x.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == (2 if self._stereo else 1)
-        out_stride = out.stride(0) // (2 if self._stereo else 1)
+            out = torch.empty((self.nchan, max(cap, 1)) + _tail(ow), dtype=odt, device=x.device)
+        assert out.is_cuda and out.dtype == odt and out.dim() == 1 + ow and out.shape[0] == self.nchan and out.shape[1] >= cap
+        assert out.stride(1) == ow and out.stride(0) % ow == 0 and (ow == 1 or (out.shape[2] == 2 and out.stride(2) == 1))
+        mid = (_in_counts_ptr(in_counts, self.nchan, x.device),) if self._takes_in_counts else ()
+        last = ()
+        if self._emits == "counts":
+            if counts is None:
+                counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
+            assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
+            last = (counts.data_ptr(),)
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._L.qdsp_hip_demod_process_batch_dev(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out_stride, stream),
-                   "qdsp_hip_demod_process_batch_dev")
-        return out[:, :n]
+        name = self._batch_fn or self._prefix + "_process_batch_dev"
+        rc = getattr(self._L, name)(self._h, x.data_ptr(), n, x.stride(0) // iw, *mid, out.data_ptr(), out.stride(0) // ow, *last, stream)
+        rc = capi.check(int(rc), name)
+        if self._emits == "counts":
+            return out[:, :cap], counts
+        return out[:, :n if self._emits == "n" else rc]
 
     def process_ex(self, x, in_link: int, count: int, out, out_link: int):
         """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
@@ -502,6 +594,52 @@ class _Demod(_Op):
 
     def set_done_event(self, ev: int):
         capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
+
+    def _time_count(self, x) -> int:
+        return x.numel() // self.nchan
+
+    def time_dev(self, x, out, iters: int) -> float:
+        """Mean ms per launch of `iters` back-to-back process_dev calls over the nchan rows of `x`, back to back
+        (qdsp_hip_time_process_dev)."""
+        import torch
+
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ms = C.c_float()
+        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), self._time_count(x), out.data_ptr(), stream, iters, C.byref(ms))
+        capi.check(rc, "qdsp_hip_time_process_dev")
+        return float(ms.value)
+
+
+class _OutSize:
+    """For a class whose calls emit at most `out_size(n)` outputs per row and return the count."""
+
+    _emits = "returned"
+
+    def out_size(self, n: int) -> int:
+        """The most outputs per row a call of `n` samples per row can emit: the slots an output row needs.  FeedForwardAgc: what
+        the next call would emit."""
+        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), self._prefix + "_out_size"))
+
+
+class _Counts(_OutSize):
+    """... and whose rows each emit a count of their own."""
+
+    _emits = "counts"
+
+    def counts(self) -> np.ndarray:
+        """The outputs per row of the last call (synchronises the device)."""
+        c = np.zeros(self.nchan, dtype=np.int32)
+        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
+        return c
+
+
+class _Demod(_Rows):
+    """Complex in, real out: one float per sample, or a stereo_t {l, r} pair (`_ow` 2).  The 1-D form of a handle of `nchan`
+    channels reads their rows back to back."""
+
+    nchan = 1
+    _np, _out_np = np.complex64, np.float32
+    _flat = True
 
 
 class FmDemod(_Demod):
@@ -513,11 +651,10 @@ class FmDemod(_Demod):
     def __init__(self, sample_rate, deviation, stereo: bool = False, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
         self.device = device
-        self._stereo = bool(stereo)
+        self._ow = 2 if stereo else 1
         self.nchan = int(nchan)
         capi.check(self._fn("create")(C.byref(self._h), device, 1 if stereo else 0, self.nchan, max_block), "qdsp_hip_demod_create")
-        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
-        devs = np.broadcast_to(np.asarray(deviation, dtype=np.float32), (self.nchan,))
+        rates, devs = _per_chan(sample_rate, self.nchan), _per_chan(deviation, self.nchan)
         for c in range(self.nchan):
             self.set_fm(float(rates[c]), float(devs[c]), c)
 
@@ -565,6 +702,7 @@ class SsbDemod(_Demod, _NcoMixin):
 
     USB, LSB, DSB = 0, 1, 2
     _prefix = "qdsp_hip_ssb_cf32"
+    _batch_fn = "qdsp_hip_demod_process_batch_dev"     # (no batch entry point of its own: the demodulators' refuses the handle)
 
     def __init__(self, sample_rate: float = None, bandwidth: float = None, mode: int = 0, phase_inc=None, device: int = 0,
                  max_block: int = 1_000_000):
@@ -578,11 +716,12 @@ class SsbDemod(_Demod, _NcoMixin):
 __all__ += ["FmDemod", "AmDemod", "SsbDemod", "ssb_phase_delta"]
 
 
-class Deemp(_Op):
+class Deemp(_Rows):
     """BFMDeemp (src/dsp/filter.h:90-173): y[i] = alpha x[i] + (1 - alpha) y[i-1], alpha = dt / (tau + dt) in float, run as
     an FP64 prefix scan (include/qdsp_hip.h).  stereo=True: stereo_t rows, shape (n, 2), l and r filtered independently;
     stereo=False: float rows.  `nchan` channels per launch, each with its own alpha and state.  numpy input: the host entry
-    point (one channel); a 1-D / (n, 2) torch tensor: *_process_dev; (nchan, n) / (nchan, n, 2): `process_batch`."""
+    point (one channel); a 1-D / (n, 2) torch tensor: *_process_dev; (nchan, n) / (nchan, n, 2): `process_batch`, where out=x
+    filters in place."""
 
     _prefix = "qdsp_hip_deemp"
 
@@ -590,16 +729,12 @@ class Deemp(_Op):
         super().__init__()
         self.device = device
         self._stereo = bool(stereo)
-        self._nc = 2 if stereo else 1
+        self._iw = self._ow = 2 if stereo else 1
         self.nchan = int(nchan)
         capi.check(self._fn("create")(C.byref(self._h), device, 1 if stereo else 0, self.nchan, max_block), "qdsp_hip_deemp_create")
-        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
-        taus = np.broadcast_to(np.asarray(tau, dtype=np.float32), (self.nchan,))
+        rates, taus = _per_chan(sample_rate, self.nchan), _per_chan(tau, self.nchan)
         for c in range(self.nchan):
             self.set(float(rates[c]), float(taus[c]), c)
-
-    def _shape(self, *lead):
-        return (*lead, 2) if self._stereo else tuple(lead)
 
     def set(self, sample_rate: float, tau: float, chan: int = -1):
         capi.check(self._fn("set")(self._h, int(chan), sample_rate, tau), "qdsp_hip_deemp_set")
@@ -624,158 +759,35 @@ class Deemp(_Op):
     def reset(self):
         capi.check(self._fn("reset")(self._h))
 
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 1 + self._nc:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=np.float32)
-        assert a.ndim == self._nc and (not self._stereo or a.shape[1] == 2), a.shape
-        n = a.shape[0]
-        y = np.empty(self._shape(max(n, 1)), dtype=np.float32)
-        capi.check(self._fn("process")(self._h, a.ctypes.data, n, y.ctypes.data), "qdsp_hip_deemp_process")
-        return y[:n]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == self._nc, "one contiguous row"
-        assert self.nchan == 1 and (not self._stereo or x.shape[1] == 2)
-        n = x.shape[0]
-        if out is None:
-            out = torch.empty(self._shape(max(n, 1)), dtype=torch.float32, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] >= n and out.dim() == x.dim()
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), "qdsp_hip_deemp_process_dev")
-        return out[:n]
-
-    def process_batch(self, x, out=None, count: int = None):
-        """Channel c = row c of the float32 tensor `x`, (nchan, n) or (nchan, n, 2) (rows may be padded: x.stride(0) beyond
-        the row, e.g. FmDemod.process_batch's output or a slice of it); out=x filters in place."""
-        import torch
-
-        nc = self._nc
-        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 + nc and x.shape[0] == self.nchan and x.stride(1) == nc
-        assert not self._stereo or (x.shape[2] == 2 and x.stride(2) == 1)
-        assert x.stride(0) % nc == 0
-        n = x.shape[1] if count is None else int(count)
-        if out is None:
-            out = torch.empty(self._shape(self.nchan, max(n, 1)), dtype=torch.float32, device=x.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.dim() == x.dim() and out.shape[0] == self.nchan
-        assert out.shape[1] >= n and out.stride(1) == nc and out.stride(0) % nc == 0
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0) // nc, out.data_ptr(), out.stride(0) // nc, stream),
-                   "qdsp_hip_deemp_process_batch_dev")
-        return out[:, :n]
-
-    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
-        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
-        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
-
-    def set_done_event(self, ev: int):
-        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
-
-    def time_dev(self, x, out, iters: int) -> float:
-        """Mean ms per launch of `iters` back-to-back process_dev calls over the one row `x` (qdsp_hip_time_process_dev)."""
-        import torch
-
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ms = C.c_float()
-        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.shape[0] // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
-        capi.check(rc, "qdsp_hip_time_process_dev")
-        return float(ms.value)
+    def _time_count(self, x) -> int:
+        return x.shape[0] // self.nchan
 
 
 __all__ += ["Deemp"]
 
 
-class _RowOp(_Op):
-    """What the handles over `nchan` channel rows share: the block-graph entry point, the completion event, reset and timing."""
+class _RowOp(_Rows):
+    """A row operator whose handle has a reset.  (The demodulators and Deemp name their own: not every one of them has one.)"""
 
     nchan = 1
-
-    def process_ex(self, x, in_link: int, count: int, out, out_link: int):
-        """The block-graph entry point on raw pointers (host or device, QDSP_HIP_LINK_* codes)."""
-        return capi.check(self._fn("process_ex")(self._h, int(x), int(in_link), int(count), int(out), int(out_link)))
-
-    def set_done_event(self, ev: int):
-        capi.check(self._L.qdsp_hip_set_done_event(self._h, C.c_void_p(ev)))
 
     def reset(self):
         capi.check(self._fn("reset")(self._h))
 
-    def time_dev(self, x, out, iters: int) -> float:
-        """Mean ms per launch of `iters` back-to-back process_dev calls over the nchan rows of `x`, back to back
-        (qdsp_hip_time_process_dev)."""
-        import torch
 
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ms = C.c_float()
-        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.numel() // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
-        capi.check(rc, "qdsp_hip_time_process_dev")
-        return float(ms.value)
-
-
-class _Level(_RowOp):
-    """One reduction over a call, then one pass over it, per channel (include/qdsp_hip.h: level blocks).  numpy input: the host
-    entry point (one channel); a 1-D torch tensor: *_process_dev; a 2-D one: one row per channel (`process_batch`)."""
-
-    _np, _tt = np.float32, "float32"
-
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=self._np)
-        assert a.ndim == 1, a.shape
-        y = np.empty(max(a.size, 1), dtype=self._np)
-        capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:a.size]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
-        n = x.numel()
-        if out is None:
-            out = torch.empty(max(n, 1), dtype=dt, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= n
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
-        return out[:n]
-
-    def process_batch(self, x, out=None, count: int = None):
-        """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count, e.g. the Channelizer's output or
-        AmDemod.process_batch's, or a slice of it); out=x works in place."""
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        if out is None:
-            out = torch.empty((self.nchan, max(n, 1)), dtype=dt, device=x.device)
-        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == 1
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), stream),
-                   self._prefix + "_process_batch_dev")
-        return out[:, :n]
-
-
-class Squelch(_Level):
+class Squelch(_RowOp):
     """dsp::Squelch (src/dsp/processing.h:424-489): a call whose mean |x| is at least `level` dB is copied, any other is
     zeroed; `nchan` channels per launch, each with its own level (a scalar or one value per channel)."""
 
     _prefix = "qdsp_hip_squelch"
-    _np, _tt = np.complex64, "complex64"
+    _np = np.complex64
 
     def __init__(self, level=-50.0, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
         capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_squelch_create")
-        levels = np.broadcast_to(np.asarray(level, dtype=np.float32), (self.nchan,))
+        levels = _per_chan(level, self.nchan)
         for c in range(self.nchan):
             self.set_level(float(levels[c]), c)
 
@@ -789,7 +801,7 @@ class Squelch(_Level):
         return bool(v.value)
 
 
-class Agc(_Level):
+class Agc(_RowOp):
     """dsp::AGC (src/dsp/processing.h:83-145): the call scaled by 1 / level; level decays by fall_rate / sample_rate dB per
     sample and follows the call's maximum.  `nchan` channels per launch, each with its own rates and level."""
 
@@ -800,8 +812,7 @@ class Agc(_Level):
         self.device = device
         self.nchan = int(nchan)
         capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_agc_create")
-        falls = np.broadcast_to(np.asarray(fall_rate, dtype=np.float32), (self.nchan,))
-        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
+        falls, rates = _per_chan(fall_rate, self.nchan), _per_chan(sample_rate, self.nchan)
         for c in range(self.nchan):
             self.set(float(falls[c]), float(rates[c]), c)
 
@@ -854,15 +865,14 @@ class StereoFmDemod(_Demod):
     `pilot_taps` (shared by all channels) default to the reference's for `sample_rate` (a scalar then)."""
 
     _prefix = "qdsp_hip_stereo_fm"
-    _stereo = True
+    _ow = 2
 
     def __init__(self, sample_rate, deviation, nchan: int = 1, pilot_taps=None, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
         self._count = 0
-        rates = np.broadcast_to(np.asarray(sample_rate, dtype=np.float32), (self.nchan,))
-        devs = np.broadcast_to(np.asarray(deviation, dtype=np.float32), (self.nchan,))
+        rates, devs = _per_chan(sample_rate, self.nchan), _per_chan(deviation, self.nchan)
         if pilot_taps is None:
             assert np.all(rates == rates[0]), "one pilot filter for all channels: pass pilot_taps"
             pilot_taps = stereo_pilot_taps(float(rates[0]))
@@ -885,18 +895,9 @@ class StereoFmDemod(_Demod):
 
     def process_batch(self, x, out=None, count: int = None):
         """Channel c = row c of the 2-D complex64 tensor `x` (rows may be padded); returns (nchan, count, 2) float32."""
-        import torch
-
-        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.complex64 and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        if out is None:
-            out = torch.empty((self.nchan, max(n, 1), 2), dtype=torch.float32, device=x.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == 2
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0) // 2, stream),
-                   "qdsp_hip_stereo_fm_process_batch_dev")
-        self._count = n
-        return out[:, :n]
+        y = super().process_batch(x, out, count)
+        self._count = y.shape[1]
+        return y
 
     def process_ex(self, x, in_link: int, count: int, out, out_link: int):
         rc = super().process_ex(x, in_link, count, out, out_link)
@@ -953,25 +954,20 @@ class StereoFmDemod(_Demod):
 
     def time_dev(self, x, out, iters: int) -> float:
         """Mean ms per call of `iters` back-to-back process_dev calls over the nchan rows of `x` (qdsp_hip_time_process_dev)."""
-        import torch
-
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ms = C.c_float()
-        rc = self._L.qdsp_hip_time_process_dev(self._h, x.data_ptr(), x.numel() // self.nchan, out.data_ptr(), stream, iters, C.byref(ms))
-        capi.check(rc, "qdsp_hip_time_process_dev")
+        ms = super().time_dev(x, out, iters)
         self._count = x.numel() // self.nchan
-        return float(ms.value)
+        return ms
 
 
 __all__ += ["StereoFmDemod", "stereo_pilot_taps"]
 
 
-class FeedForwardAgc(_RowOp):
+class FeedForwardAgc(_OutSize, _RowOp):
     """dsp::FeedForwardAGC<T> (src/dsp/processing.h:147-233): every sample divided by the peak of the `window` samples from it on
     (a sliding-window maximum, floor 1e-4).  `kind_or_dtype`: 0 / "real" / float32 for float rows, 1 / "complex" / complex64 for
     complex_t rows (the level follows |re| alone, as the reference's fastAmplitude does).  The output lags the input by
     window - 1 samples: a call of n samples returns `out_size(n)` outputs, none at all while the history fills.  `nchan` rows per
-    launch share one fill."""
+    launch share one fill.  `out` may not overlap the input."""
 
     _prefix = "qdsp_hip_ffagc"
     REAL, COMPLEX = 0, 1
@@ -980,26 +976,14 @@ class FeedForwardAgc(_RowOp):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
-        self.kind = self._kind_of(kind_or_dtype)
-        self._np, self._tt = (np.complex64, "complex64") if self.kind == self.COMPLEX else (np.float32, "float32")
+        self.kind = _parse_kind(kind_or_dtype, _REAL_COMPLEX, "FeedForwardAgc")
+        self._np = _row_type(self.kind)
         self.window = int(window)
         capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, max_block, self.window), "qdsp_hip_ffagc_create")
 
     @classmethod
     def _kind_of(cls, k) -> int:
-        if isinstance(k, (int, np.integer)) and not isinstance(k, bool):
-            return int(k)
-        if isinstance(k, str) and k in ("real", "complex"):
-            return cls.COMPLEX if k == "complex" else cls.REAL
-        name = str(k).rsplit(".", 1)[-1]           # numpy and torch dtypes and scalar types alike
-        for want, kind in (("complex64", cls.COMPLEX), ("float32", cls.REAL)):
-            if want in name:
-                return kind
-        raise ValueError(f"FeedForwardAgc: float32 or complex64 rows, not {k!r}")
-
-    def out_size(self, n: int) -> int:
-        """What the next call of `n` samples (per row) would emit."""
-        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), "qdsp_hip_ffagc_out_size"))
+        return _parse_kind(k, _REAL_COMPLEX, cls.__name__)
 
     def fill(self) -> int:
         """The samples taken in and not yet output (per row)."""
@@ -1014,52 +998,11 @@ class FeedForwardAgc(_RowOp):
         h = np.ascontiguousarray(hist, dtype=self._np)
         capi.check(self._fn("set_history")(self._h, int(chan), h.ctypes.data, h.size), "qdsp_hip_ffagc_set_history")
 
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=self._np)
-        assert a.ndim == 1, a.shape
-        y = np.empty(max(self.out_size(a.size), 1), dtype=self._np)
-        no = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:no]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
-        n = x.numel()
-        if out is None:
-            out = torch.empty(max(self.out_size(n), 1), dtype=dt, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= self.out_size(n)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        no = capi.check(int(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream)), self._prefix + "_process_dev")
-        return out[:no]
-
-    def process_batch(self, x, out=None, count: int = None):
-        """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count); returns the (nchan, out_size(count))
-        view of `out`.  `out` may not overlap `x`."""
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        no = self.out_size(n)
-        if out is None:
-            out = torch.empty((self.nchan, max(no, 1)), dtype=dt, device=x.device)
-        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= no and out.stride(1) == 1
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), stream)
-        no = capi.check(int(rc), self._prefix + "_process_batch_dev")
-        return out[:, :no]
-
 
 __all__ += ["FeedForwardAgc"]
 
 
-class ComplexAgc(_Level):
+class ComplexAgc(_RowOp):
     """dsp::ComplexAGC (src/dsp/processing.h:235-298): out[i] = x[i] g; g += (set_point - |out[i]|) rate; g = min(g, max_gain),
     per sample, run as an FP64 clamped prefix scan (include/qdsp_hip.h: complex AGC).  `nchan` complex64 rows per launch, each
     with its own parameters (scalars or one value per channel) and gain.  A row the scan does not cover in a call -- a NaN or Inf
@@ -1067,16 +1010,14 @@ class ComplexAgc(_Level):
     instead, serially.  Entry points by input as for Squelch and Agc; out=x works in place."""
 
     _prefix = "qdsp_hip_cagc"
-    _np, _tt = np.complex64, "complex64"
+    _np = np.complex64
 
     def __init__(self, set_point=1.0, max_gain=1e5, rate=1e-3, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
         capi.check(self._fn("create")(C.byref(self._h), device, self.nchan, max_block), "qdsp_hip_cagc_create")
-        sps = np.broadcast_to(np.asarray(set_point, dtype=np.float32), (self.nchan,))
-        mgs = np.broadcast_to(np.asarray(max_gain, dtype=np.float32), (self.nchan,))
-        rts = np.broadcast_to(np.asarray(rate, dtype=np.float32), (self.nchan,))
+        sps, mgs, rts = _per_chan(set_point, self.nchan), _per_chan(max_gain, self.nchan), _per_chan(rate, self.nchan)
         for c in range(self.nchan):
             self.set(float(sps[c]), float(mgs[c]), float(rts[c]), c)
 
@@ -1097,14 +1038,14 @@ class ComplexAgc(_Level):
 __all__ += ["ComplexAgc"]
 
 
-class CostasLoop(_Level):
+class CostasLoop(_RowOp):
     """dsp::CostasLoop<ORDER> (src/dsp/pll.h:47-102), ORDER 2, 4 or 8: out = vco x; the order's phase error of out, clamped, moves
     the frequency (beta) and the phase (alpha); vco = exp(-j phase).  One row per lane, 16 rows to a wave (include/qdsp_hip.h: Costas
     loop).  `nchan` complex64 rows per launch, each with its own loop bandwidth (a scalar or one value per channel), frequency and
     phase (FP64, on the device).  Entry points by input as for Squelch and Agc; out=x works in place."""
 
     _prefix = "qdsp_hip_costas"
-    _np, _tt = np.complex64, "complex64"
+    _np = np.complex64
 
     def __init__(self, order: int, bandwidth, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
@@ -1112,7 +1053,7 @@ class CostasLoop(_Level):
         self.order = int(order)
         self.nchan = int(nchan)
         capi.check(self._fn("create")(C.byref(self._h), device, self.order, self.nchan, max_block), "qdsp_hip_costas_create")
-        bws = np.broadcast_to(np.asarray(bandwidth, dtype=np.float32), (self.nchan,))
+        bws = _per_chan(bandwidth, self.nchan)
         if np.all(bws == bws[0]):
             self.set_bandwidth(float(bws[0]))
         else:
@@ -1142,7 +1083,7 @@ class CostasLoop(_Level):
 __all__ += ["CostasLoop"]
 
 
-class MmClockRecovery(_RowOp):
+class MmClockRecovery(_Counts, _RowOp):
     """dsp::MMClockRecovery<T> (src/dsp/clock_recovery.h:68-243): Mueller & Mueller symbol timing.  Every symbol is the 8-tap MMSE
     interpolation of the input at the loop's position (129 fractional steps, the table in `interp_taps()`), and the type's phase
     error of the symbol moves the symbol period (`gain_omega`, within omega (1 +- rel_limit)) and the position (`mu_gain`).
@@ -1159,19 +1100,23 @@ class MmClockRecovery(_RowOp):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
-        self.kind = FeedForwardAgc._kind_of(kind_or_dtype)
-        self._np, self._tt = (np.complex64, "complex64") if self.kind == self.COMPLEX else (np.float32, "float32")
-        par = [np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,)) for v in (omega, gain_omega, mu_gain, rel_limit)]
+        self.kind = _parse_kind(kind_or_dtype, _REAL_COMPLEX, "MmClockRecovery")
+        self._np = _row_type(self.kind)
+        par = [_per_chan(v, self.nchan) for v in (omega, gain_omega, mu_gain, rel_limit)]
         capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, max_block, *(float(v[0]) for v in par)),
                    "qdsp_hip_mmcr_create")
         if any(np.any(v != v[0]) for v in par):
-            for c in range(self.nchan):
-                # (one at a time a change may leave the rule for a moment: gains and limit that fit every omega first)
-                self.set_gains(0.0, 0.0, c)
-                self.set_limit(0.0, c)
-                self.set_omega(float(par[0][c]), c)
-                self.set_limit(float(par[3][c]), c)
-                self.set_gains(float(par[1][c]), float(par[2][c]), c)
+            self._set_rows(par)
+
+    def _set_rows(self, par):
+        """omega, gain_omega, mu_gain and rel_limit of every channel, in an order in which no step leaves the parameter rule."""
+        for c in range(self.nchan):
+            # (one at a time a change may leave the rule for a moment: gains and limit that fit every omega first)
+            self.set_gains(0.0, 0.0, c)
+            self.set_limit(0.0, c)
+            self.set_omega(float(par[0][c]), c)
+            self.set_limit(float(par[3][c]), c)
+            self.set_gains(float(par[1][c]), float(par[2][c]), c)
 
     def set_omega(self, omega: float, chan: int = -1):
         """Samples per symbol; also restarts the loop's period there.  Takes effect from the next call."""
@@ -1192,10 +1137,6 @@ class MmClockRecovery(_RowOp):
     def set_state(self, mu: float, dyn_omega: float, next: int, chan: int = -1):
         capi.check(self._fn("set_state")(self._h, int(chan), float(mu), float(dyn_omega), int(next)), "qdsp_hip_mmcr_set_state")
 
-    def out_size(self, n: int) -> int:
-        """The most symbols per row a call of `n` samples can emit: the slots an output row needs."""
-        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), "qdsp_hip_mmcr_out_size"))
-
     def interp_taps(self) -> np.ndarray:
         t = np.zeros((129, 8), dtype=np.float32)
         capi.check(self._fn("get_interp_taps")(self._h, t.ctypes.data_as(C.POINTER(C.c_float))))
@@ -1206,62 +1147,17 @@ class MmClockRecovery(_RowOp):
         assert t.shape == (129, 8), t.shape
         capi.check(self._fn("set_interp_taps")(self._h, t.ctypes.data_as(C.POINTER(C.c_float))), "qdsp_hip_mmcr_set_interp_taps")
 
-    def counts(self) -> np.ndarray:
-        """The symbols per row of the last call (synchronises the device)."""
-        c = np.zeros(self.nchan, dtype=np.int32)
-        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
-        return c
-
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=self._np)
-        assert a.ndim == 1, a.shape
-        y = np.empty(max(self.out_size(a.size), 1), dtype=self._np)
-        no = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:no]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
-        n = x.numel()
-        if out is None:
-            out = torch.empty(max(self.out_size(n), 1), dtype=dt, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= self.out_size(n)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
-        return out[:int(self.counts()[0])]
-
     def process_batch(self, x, out=None, count: int = None, counts=None):
         """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count).  Returns (rows, counts): the
         (nchan, out_size(count)) view of `out`, row c's symbols in its first counts[c] slots and the rest untouched, and the
         counts as an int32 device tensor (`counts`, or a new one).  Asynchronous; `out` may not overlap `x`."""
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        no = self.out_size(n)
-        if out is None:
-            out = torch.empty((self.nchan, max(no, 1)), dtype=dt, device=x.device)
-        if counts is None:
-            counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
-        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= no and out.stride(1) == 1
-        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), counts.data_ptr(), stream)
-        capi.check(int(rc), self._prefix + "_process_batch_dev")
-        return out[:, :no], counts
+        return self._batch(x, out, count, counts=counts)
 
 
 __all__ += ["MmClockRecovery"]
 
 
-class RowFir(_Level):
+class RowFir(_RowOp):
     """dsp::FIR<T> (src/dsp/filter.h:51-74) over `nchan` channel rows in one launch (include/qdsp_hip.h: FIR over channel rows):
     y[c][i] = sum_k taps[c][k] x[c][i - (T - 1) + k], every output component the chain acc = fmaf(taps[k], x, acc) in tap order --
     the bits of `Fir(...).set_mode(Fir.DIRECT)` row by row.  `kind_or_dtype` as for MmClockRecovery (float32 or complex64 rows);
@@ -1275,8 +1171,8 @@ class RowFir(_Level):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
-        self.kind = FeedForwardAgc._kind_of(kind_or_dtype)
-        self._set_kind()
+        self.kind = _parse_kind(kind_or_dtype, _REAL_COMPLEX, "RowFir")
+        self._np = _row_type(self.kind)
         t = np.ascontiguousarray(taps, dtype=np.float32)
         first, p = _taps_ptr(t if t.ndim == 1 else t[0])
         capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, p, len(first), max_block), "qdsp_hip_rowfir_create")
@@ -1284,9 +1180,6 @@ class RowFir(_Level):
             assert t.shape[0] == self.nchan, t.shape
             for c in range(1, self.nchan):
                 self.set_taps(t[c], c)
-
-    def _set_kind(self):
-        self._np, self._tt = (np.complex64, "complex64") if self.kind == self.COMPLEX else (np.float32, "float32")
 
     @classmethod
     def tile(cls) -> int:
@@ -1317,12 +1210,12 @@ class RowFir(_Level):
         capi.check(self._fn("set_history")(self._h, int(chan), a.ctypes.data))
 
 
-class DelayImag(_Level):
+class DelayImag(_RowOp):
     """dsp::DelayImag (src/dsp/processing.h:300-344), the one-sample Q delay of offset PSK: out[i] = {x[i].re, x[i - 1].im}, bit
     copies, over `nchan` complex64 rows.  Entry points by input as for Squelch and Agc; `out` may not overlap the input."""
 
     _prefix = "qdsp_hip_delay_imag"
-    _np, _tt = np.complex64, "complex64"
+    _np = np.complex64
 
     def __init__(self, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
@@ -1385,12 +1278,12 @@ def _borrowed(cls, handle, **attrs):
     return v
 
 
-class _Chain(_RowOp):
+class _Chain(_Counts, _RowOp):
     """What PskDemod and MskDemod share: a chain handle (include/qdsp_hip.h: PSKDemod and MSKDemod) runs every stage over `nchan`
     rows in one call with the intermediates on the device.  numpy input: the host entry point (one channel), returning the
     symbols; a 1-D tensor: *_process_dev; a 2-D one: `process_batch`, returning (rows, counts)."""
 
-    _sym_np, _sym_tt = np.complex64, "complex64"
+    _np = np.complex64
 
     def stage(self, which: int):
         """A non-owning view of stage `which` with that operator's methods (setters, getters, state); never process on it."""
@@ -1419,68 +1312,15 @@ class _Chain(_RowOp):
         t = torch.view_as_complex(t.view(self.nchan, st.value, 2)) if cplx else t.view(self.nchan, st.value)
         return t if count is None else t[:, :int(count)]
 
-    def out_size(self, n: int) -> int:
-        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), self._prefix + "_out_size"))
-
-    def counts(self) -> np.ndarray:
-        """The symbols per row of the last call (synchronises the device)."""
-        c = np.zeros(self.nchan, dtype=np.int32)
-        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
-        return c
-
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=np.complex64)
-        assert a.ndim == 1, a.shape
-        y = np.empty(max(self.out_size(a.size), 1), dtype=self._sym_np)
-        no = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:no]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        dt = getattr(torch, self._sym_tt)
-        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.complex64 and x.dim() == 1 and self.nchan == 1, "one contiguous row"
-        n = x.numel()
-        if out is None:
-            out = torch.empty(max(self.out_size(n), 1), dtype=dt, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == dt and out.numel() >= self.out_size(n)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
-        return out[:int(self.counts()[0])]
-
     def process_batch(self, x, out=None, count: int = None, counts=None):
         """Channel c = row c of the 2-D complex64 tensor `x` (rows may be padded).  Returns (rows, counts) as
         MmClockRecovery.process_batch does.  Asynchronous."""
-        import torch
-
-        dt = getattr(torch, self._sym_tt)
-        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.complex64 and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        no = self.out_size(n)
-        if out is None:
-            out = torch.empty((self.nchan, max(no, 1)), dtype=dt, device=x.device)
-        if counts is None:
-            counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
-        assert out.is_cuda and out.dtype == dt and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= no and out.stride(1) == 1
-        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), out.data_ptr(), out.stride(0), counts.data_ptr(), stream)
-        capi.check(int(rc), self._prefix + "_process_batch_dev")
-        return out[:, :no], counts
+        return self._batch(x, out, count, counts=counts)
 
     def _set_clock(self, clock, omega, gain_omega, mu_gain, rel_limit):
-        par = [np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,)) for v in (omega, gain_omega, mu_gain, rel_limit)]
+        par = [_per_chan(v, self.nchan) for v in (omega, gain_omega, mu_gain, rel_limit)]
         if any(np.any(v != v[0]) for v in par):
-            for c in range(self.nchan):   # (the order of MmClockRecovery.__init__: no step leaves the parameter rule)
-                clock.set_gains(0.0, 0.0, c)
-                clock.set_limit(0.0, c)
-                clock.set_omega(float(par[0][c]), c)
-                clock.set_limit(float(par[3][c]), c)
-                clock.set_gains(float(par[1][c]), float(par[2][c]), c)
+            clock._set_rows(par)   # (the order of MmClockRecovery.__init__: no step leaves the parameter rule)
 
 
 class PskDemod(_Chain):
@@ -1500,7 +1340,7 @@ class PskDemod(_Chain):
         self.device = device
         self.nchan = int(nchan)
         self.order, self.offset = int(order), bool(offset)
-        b = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,))   # noqa: E731
+        b = lambda v: _per_chan(v, self.nchan)   # noqa: E731
         sr, baud, alpha, rate, bw = b(sample_rate), b(baud_rate), b(rrc_alpha), b(agc_rate), b(costas_bw)
         taps = [rrc_taps(rrc_tap_count, sr[c], baud[c], alpha[c]) for c in range(self.nchan)]
         omega = (sr / baud).astype(np.float32)
@@ -1526,14 +1366,12 @@ class PskDemod(_Chain):
         if which == self.AGC:
             return _borrowed(ComplexAgc, handle, nchan=self.nchan, device=self.device)
         if which == self.RRC:
-            v = _borrowed(RowFir, handle, nchan=self.nchan, device=self.device, kind=RowFir.COMPLEX)
-            v._set_kind()
-            return v
+            return _borrowed(RowFir, handle, nchan=self.nchan, device=self.device, kind=RowFir.COMPLEX, _np=np.complex64)
         if which == self.COSTAS:
             return _borrowed(CostasLoop, handle, nchan=self.nchan, device=self.device, order=self.order)
         if which == self.DELAY:
             return _borrowed(DelayImag, handle, nchan=self.nchan, device=self.device)
-        return _borrowed(MmClockRecovery, handle, nchan=self.nchan, device=self.device, kind=1, _np=np.complex64, _tt="complex64")
+        return _borrowed(MmClockRecovery, handle, nchan=self.nchan, device=self.device, kind=1, _np=np.complex64)
 
 
 class MskDemod(_Chain):
@@ -1542,7 +1380,7 @@ class MskDemod(_Chain):
     forwarded (the reference's constructor drops them).  `stage(MskDemod.FM / CLOCK)`, `tap(MskDemod.FM)`."""
 
     _prefix = "qdsp_hip_msk"
-    _sym_np, _sym_tt = np.float32, "float32"
+    _out_np = np.float32
     FM, CLOCK = 0, 1
 
     def __init__(self, sample_rate, deviation, baud_rate, omega_gain=0.01 * 0.01 / 4, mu_gain=0.01, omega_rel_limit=0.005,
@@ -1550,7 +1388,7 @@ class MskDemod(_Chain):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
-        b = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float32), (self.nchan,))   # noqa: E731
+        b = lambda v: _per_chan(v, self.nchan)   # noqa: E731
         sr, dev, baud = b(sample_rate), b(deviation), b(baud_rate)
         omega = (sr / baud).astype(np.float32)
         go, gm, rl = b(omega_gain), b(mu_gain), b(omega_rel_limit)
@@ -1568,21 +1406,10 @@ class MskDemod(_Chain):
     def _view(self, which: int, handle):
         if which == self.FM:
             return _borrowed(FmDemod, handle, nchan=self.nchan, device=self.device)
-        return _borrowed(MmClockRecovery, handle, nchan=self.nchan, device=self.device, kind=0, _np=np.float32, _tt="float32")
+        return _borrowed(MmClockRecovery, handle, nchan=self.nchan, device=self.device, kind=0, _np=np.float32)
 
 
 __all__ += ["RowFir", "DelayImag", "PskDemod", "MskDemod", "rrc_taps"]
-
-
-def _in_counts_ptr(in_counts, nchan, device):
-    """The device pointer of an optional int32 tensor of per-row input counts (None: every row has the call's count)."""
-    import torch
-
-    if in_counts is None:
-        return None
-    assert in_counts.is_cuda and in_counts.dtype == torch.int32 and in_counts.is_contiguous() and in_counts.numel() == nchan
-    assert in_counts.device == device
-    return in_counts.data_ptr()
 
 
 class Threshold(_RowOp):
@@ -1591,6 +1418,8 @@ class Threshold(_RowOp):
     `process_batch`.  No state: `reset` does nothing."""
 
     _prefix = "qdsp_hip_threshold"
+    _out_np = np.uint8
+    _takes_in_counts = True
 
     def __init__(self, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
@@ -1609,47 +1438,13 @@ class Threshold(_RowOp):
     def out_size(self, n: int) -> int:
         return int(n)
 
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=np.float32)
-        assert a.ndim == 1, a.shape
-        y = np.empty(max(a.size, 1), dtype=np.uint8)
-        capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:a.size]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 1 and self.nchan == 1, "one contiguous row"
-        n = x.numel()
-        if out is None:
-            out = torch.empty(max(n, 1), dtype=torch.uint8, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= n
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
-        return out[:n]
-
     def process_batch(self, x, out=None, count: int = None, in_counts=None):
         """Channel c = row c of the 2-D float32 tensor `x` (rows may be padded).  `in_counts`: an int32 device tensor, row c
         converts min(max(in_counts[c], 0), count) floats and leaves the rest of its output row untouched.  Asynchronous."""
-        import torch
-
-        assert x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        if out is None:
-            out = torch.empty((self.nchan, max(n, 1)), dtype=torch.uint8, device=x.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= n and out.stride(1) == 1
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), _in_counts_ptr(in_counts, self.nchan, x.device),
-                                           out.data_ptr(), out.stride(0), stream)
-        capi.check(int(rc), self._prefix + "_process_batch_dev")
-        return out[:, :n]
+        return self._batch(x, out, count, in_counts=in_counts)
 
 
-class Deframer(_RowOp):
+class Deframer(_Counts, _RowOp):
     """dsp::Deframer (src/dsp/deframing.h): finds `sync` (one bit per byte) in rows of one bit per byte, cuts frames of `frame_len`
     bits and packs them eight to a byte (include/qdsp_hip.h: Deframer).  `kind_or_dtype`: 0 / "bytes" / uint8 for uint8 rows,
     1 / "float" / float32 for float32 soft symbols thresholded on load.  `nchan` rows per launch, each with its own state.  A call
@@ -1657,26 +1452,25 @@ class Deframer(_RowOp):
     `process_batch` the padded rows and the per-row frame counts."""
 
     _prefix = "qdsp_hip_deframer"
+    _out_np = np.uint8
+    _takes_in_counts = True
     BYTES, FLOAT = 0, 1
 
     def __init__(self, frame_len: int, sync, kind_or_dtype=0, nchan: int = 1, device: int = 0, max_block: int = 1_000_000):
         super().__init__()
         self.device = device
         self.nchan = int(nchan)
-        k = kind_or_dtype if isinstance(kind_or_dtype, (int, str)) else getattr(kind_or_dtype, "__name__", str(kind_or_dtype))
-        if k in (0, "bytes", "uint8", "torch.uint8"):
-            self.kind = self.BYTES
-        elif k in (1, "float", "float32", "torch.float32"):
-            self.kind = self.FLOAT
-        else:
-            raise ValueError(f"kind_or_dtype: {kind_or_dtype!r}")
-        self._np, self._tt = (np.float32, "float32") if self.kind else (np.uint8, "uint8")
+        self.kind = _parse_kind(kind_or_dtype, (("bytes", "uint8"), ("float", "float32")), "Deframer", exact=True)
+        self._np = np.float32 if self.kind else np.uint8
         s = np.ascontiguousarray(sync, dtype=np.uint8).ravel()
         self.frame_len = int(frame_len)
         capi.check(self._fn("create")(C.byref(self._h), device, self.kind, self.nchan, max_block, self.frame_len, s.ctypes.data, s.size),
                    "qdsp_hip_deframer_create")
         self.sync_len = int(s.size)
-        self.frame_bytes = int(self._fn("frame_bytes")(self._h))
+        self._per = self.frame_bytes = int(self._fn("frame_bytes")(self._h))
+
+    def _result(self, y):
+        return y.reshape(y.shape[0] // self.frame_bytes, self.frame_bytes)
 
     @staticmethod
     def tile() -> int:
@@ -1701,65 +1495,13 @@ class Deframer(_RowOp):
     def set_state(self, bits_read: int, bad: int, after: bool, chan: int = -1):
         capi.check(self._fn("set_state")(self._h, int(chan), int(bits_read), int(bad), int(bool(after))), "qdsp_hip_deframer_set_state")
 
-    def out_size(self, n: int) -> int:
-        """The most frames per row a call of `n` bytes can emit."""
-        return int(capi.check(int(self._fn("out_size")(self._h, int(n))), "qdsp_hip_deframer_out_size"))
-
-    def counts(self) -> np.ndarray:
-        """The frames per row of the last call (synchronises the device)."""
-        c = np.zeros(self.nchan, dtype=np.int32)
-        capi.check(self._fn("get_counts")(self._h, c.ctypes.data_as(C.POINTER(C.c_int))))
-        return c
-
-    def process(self, x, out=None):
-        if _is_torch(x):
-            if x.dim() == 2:
-                return self.process_batch(x, out)
-            return self._process_dev(x, out)
-        a = np.ascontiguousarray(x, dtype=self._np)
-        assert a.ndim == 1, a.shape
-        y = np.empty((max(self.out_size(a.size), 1), self.frame_bytes), dtype=np.uint8)
-        nf = capi.check(self._fn("process")(self._h, a.ctypes.data, a.size, y.ctypes.data), self._prefix + "_process")
-        return y[:nf]
-
-    def _process_dev(self, x, out=None):
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.is_contiguous() and x.dtype == dt and x.dim() == 1 and self.nchan == 1, "one contiguous row"
-        n = x.numel()
-        nb = self.out_size(n) * self.frame_bytes
-        if out is None:
-            out = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
-        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and out.numel() >= nb
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(self._fn("process_dev")(self._h, x.data_ptr(), n, out.data_ptr(), stream), self._prefix + "_process_dev")
-        nf = int(self.counts()[0])
-        return out[:nf * self.frame_bytes].view(nf, self.frame_bytes)
-
     def process_batch(self, x, out=None, count: int = None, in_counts=None, counts=None):
         """Channel c = row c of the 2-D tensor `x` (rows may be padded: x.stride(0) >= count).  `in_counts`: an int32 device
         tensor of per-row input counts (what MmClockRecovery.process_batch or a chain returns), row c takes
         min(max(in_counts[c], 0), count) of its elements.  Returns (rows, counts): the (nchan, out_size(count) * frame_bytes) uint8
         view of `out`, row c's frames back to back in its first counts[c] * frame_bytes bytes and the rest untouched, and the
         frame counts as an int32 device tensor (`counts`, or a new one).  Asynchronous; `out` may not overlap `x`."""
-        import torch
-
-        dt = getattr(torch, self._tt)
-        assert x.is_cuda and x.dim() == 2 and x.dtype == dt and x.shape[0] == self.nchan and x.stride(1) == 1
-        n = x.shape[1] if count is None else int(count)
-        nb = self.out_size(n) * self.frame_bytes
-        if out is None:
-            out = torch.empty((self.nchan, max(nb, 1)), dtype=torch.uint8, device=x.device)
-        if counts is None:
-            counts = torch.empty(self.nchan, dtype=torch.int32, device=x.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == self.nchan and out.shape[1] >= nb and out.stride(1) == 1
-        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == self.nchan
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self._fn("process_batch_dev")(self._h, x.data_ptr(), n, x.stride(0), _in_counts_ptr(in_counts, self.nchan, x.device),
-                                           out.data_ptr(), out.stride(0), counts.data_ptr(), stream)
-        capi.check(int(rc), self._prefix + "_process_batch_dev")
-        return out[:, :nb], counts
+        return self._batch(x, out, count, in_counts, counts)
 
     def time_dev(self, x, out, iters: int) -> float:
         """Mean ms per call of `iters` back-to-back process_batch calls over the rows of the 2-D tensor `x` (HIP events on the
