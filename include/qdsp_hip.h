@@ -822,6 +822,63 @@ void qdsp_hip_deframer_destroy(void* h);
 int qdsp_hip_deframer_tile(void);
 int qdsp_hip_deframer_pack_span(void);
 
+/* ---- Reed-Solomon decoder and FalconRS : src/dsp/falcon_fec.h, src/libcorrect/reed-solomon ------ */
+/* Reed-Solomon decoding over GF(2^8) of interleaved frames, nchan channel-major rows of frames per call; every count of this
+ * section is in FRAMES.  Stateless per frame.  Per handle: the primitive polynomial (9 bits, degree 8; one that is not primitive
+ * is QDSP_HIP_EINVAL), first_root (0 .. 255), root_gap (gcd(root_gap, 255) = 1), num_roots (2 .. 32), the interleave depth I
+ * (1 .. 8), skip (0 .. 64: bytes in front of the interleaved block, a sync word say), full_out (0 / 1) and optionally a 256-byte
+ * input map, a 256-byte output map (NULL: the identity) and an XOR sequence of xor_len bytes, 1 .. 255 I (NULL: none).  Only
+ * full-length codewords of 255 bytes.  A frame is frame_in_bytes = skip + 255 I bytes; with k = 255 - num_roots and d = in + skip:
+ *   cw[c][p] = in_map[d[p I + c]], c < I, p < 255
+ *   msg[c][0 .. k) = libcorrect's correct_reed_solomon_decode(cw[c], 255); the frame is good only if all I codewords decode
+ *   out[i] = out_map[p < k ? msg[i % I][p] : 0] ^ xor[i % xor_len], p = i / I, for i < frame_out_bytes = (full_out ? 255 : k) I
+ *   (full_out 1 is the reference block's: its output buffers keep their zeros behind byte k).
+ * The decode is libcorrect's, bit for bit, also where it is not the textbook's.  With exp[i] = alpha^i, log[alpha^i] = i for
+ * i = 1 .. 255 (so log 1 = 255) and coeff[i] = cw[254 - i]:
+ *   S[i] = coeff(alpha^(root_gap (first_root + i))), i < num_roots; all zero: msg = cw[0 .. k), 0 symbols corrected.
+ *   Locator: its Berlekamp-Massey loop (reed-solomon/decode.c:32-118), with its two coefficient arrays, its delay and the ORDER
+ *     it tracks -- last order + delay where the register grows, the maximum of that and the order before where it does not; it is
+ *     not the degree -- kept exactly; the discrepancy at step i runs over coefficients 1 .. numerrors.
+ *   Roots: the x among all 256 elements with sum_{j <= order} Lambda[j] x^j = 0.  The codeword fails exactly when their number
+ *     differs from the order.
+ *   Per root x: the coefficient index is ((255 - log x) root_gap^-1) mod 255 (so 1 / x = 1 gives coefficient 0) and the value
+ *     x^(first_root - 1) Omega(x) / Lambda'(x), Omega = S Lambda mod x^num_roots, Lambda' the formal derivative of the truncated
+ *     locator, x / 0 = 0; the value is XOR-ed into the coefficient.  msg[i] = coeff[254 - i], i < k.
+ *   A word with more than num_roots / 2 errors that this procedure takes to another codeword comes out as that codeword.
+ *   One departure: an order equal to num_roots makes libcorrect read one byte past its table of powers; here the power is computed.
+ * Good frames of a row go back to back into the row's first output slots, in input order; dropped frames leave no gap; the bytes
+ * behind the last good frame are not touched.
+ * process_batch_dev: asynchronous, three launches on hip_stream.  in_stride_bytes >= nframes * frame_in_bytes, out_stride_bytes >=
+ * nframes * frame_out_bytes, any byte alignment of rows; d_in_counts: int32[nchan] on the device or NULL, row r has
+ * min(max(d_in_counts[r], 0), nframes) frames (qdsp_hip_deframer's d_counts fits, so the two run on one stream with no host
+ * synchronisation); d_counts: good frames per row, int32[nchan], may be NULL, also kept in the handle (get_counts); d_errs:
+ * int32[nchan][nframes * I], may be NULL: per codeword -1 if it failed, else the symbols libcorrect corrected (the order its
+ * locator search returned; 0 when the syndromes are zero); for a row shorter than nframes the entries behind its count are not
+ * touched.  nframes == 0 moves nothing and clears the counts.  Overlapping d_in / d_out, a short stride and nframes > 2^22 are
+ * QDSP_HIP_EINVAL.  Decoded frames pass through library-owned scratch sized for max_block frames at create (a larger device call
+ * grows it and synchronises the device once).
+ * process_dev: the rows back to back.  process / process_ex (nchan 1): `nframes` whole frames at `in`, `out` holds nframes *
+ * frame_out_bytes; they return the good-frame count; the output link is QDSP_HIP_LINK_HOST or _DEVICE only; nframes <= max_block
+ * where a side is on the host (else QDSP_HIP_ESIZE).  out_size(nframes) = nframes.  set_maps replaces the two maps and the XOR
+ * sequence (NULL as at create), synchronises the device and acts from the next call; get_counts synchronises.
+ * qdsp_hip_last_kernel reports the decode launch.
+ * falcon_rs_create: the preset of dsp::FalconRS -- (0x187, 120, 11, 16), I = 5, skip = 4, full_out = 1, the CCSDS dual-basis maps
+ * (in: from the dual basis, out: to it) and the CCSDS randomiser as the XOR sequence, all three computed from their closed forms. */
+int qdsp_hip_rs_create(void** h, int device, int nchan, int max_block, int prim_poly, int first_root, int root_gap, int num_roots, int depth,
+                       int skip, int full_out, const uint8_t* in_map, const uint8_t* out_map, const uint8_t* xor_seq, int xor_len);
+int qdsp_hip_falcon_rs_create(void** h, int device, int nchan, int max_block);
+int qdsp_hip_rs_set_maps(void* h, const uint8_t* in_map, const uint8_t* out_map, const uint8_t* xor_seq, int xor_len);
+int64_t qdsp_hip_rs_out_size(void* h, int64_t nframes);
+int qdsp_hip_rs_frame_in_bytes(void* h);
+int qdsp_hip_rs_frame_out_bytes(void* h);
+int qdsp_hip_rs_process(void* h, const uint8_t* in, int nframes, uint8_t* out);
+int qdsp_hip_rs_process_ex(void* h, const void* in, int in_link, int nframes, void* out, int out_link);
+int qdsp_hip_rs_process_dev(void* h, const void* d_in, int64_t nframes, void* d_out, void* hip_stream);
+int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, int64_t in_stride_bytes, const int* d_in_counts, void* d_out,
+                                  int64_t out_stride_bytes, int* d_counts, int* d_errs, void* hip_stream);
+int qdsp_hip_rs_get_counts(void* h, int* counts);
+void qdsp_hip_rs_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

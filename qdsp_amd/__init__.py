@@ -6,6 +6,7 @@ Layout
                  HIP-backed FIR, PolyphaseResampler, FrequencyXlator, VFO blocks)
     capi.py      ctypes binding of the C ABI
     ops.py       operator-level front-end used by tests/ and bench.py
+    fec.py       forward error correction on the same plumbing: the Reed-Solomon decoder and FalconRS
     sharding.py  time-axis chunking of one IQ stream over ranks with an (ntaps-1) halo
 
 Nothing in this package imports oracle/ (the CPU checker); there is no CPU fallback.

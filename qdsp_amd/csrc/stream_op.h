@@ -1,5 +1,5 @@
 // stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr /
-// rowfir / deframe .hip, psk_chain.cpp):
+// rowfir / deframe / rs .hip, psk_chain.cpp):
 // the head of the handle, its creation and release, and the one block-graph path (*_process_ex) and timing loop behind all of
 // them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
@@ -73,6 +73,7 @@ int64_t launch_as(StreamOp* op, const void* d_in, int64_t count, int64_t in_stri
 // taken, for a handle that is none of the eleven.
 constexpr int kKindThreshold = 1;
 constexpr int kKindDeframer = 2;
+constexpr int kKindRs = 3;               // rs.hip.h: the Reed-Solomon decoder and its FalconRS preset
 void stream_op_register(StreamOp* d, int kind);
 void stream_op_unregister(StreamOp* d);
 // h if it is a live registered handle of `kind` (0: of any kind)
