@@ -8,6 +8,15 @@ import numpy as np
 
 N = 255
 
+# The codes of tests/golden/rs_ref_codes.npz (tests/golden/make_rs_codes.py records libcorrect's answers for them): num_roots off
+# the kernel's grid of four syndromes per dword, the smallest and the largest it takes, first roots 0 and 255, gaps 2, 7 and 254.
+ODD_CODES = ((0x11d, 1, 1, 2), (0x11d, 0, 1, 3), (0x187, 255, 2, 5), (0x12b, 7, 254, 6), (0x11d, 1, 1, 7), (0x187, 112, 11, 10),
+             (0x11d, 0, 1, 30), (0x12d, 3, 7, 31))
+# kind_i of that file: 0 .. t = that many errors at random places, and
+KIND_ENDS, KIND_PARITY, KIND_LANE63 = 100, 101, 102    # errors in byte 0 and byte 254; in the parity only; in coefficients 252 .. 254
+KIND_STRADDLE = {64: 103, 128: 104, 192: 105}          # t errors whose locator roots lie around that element of the root search
+KIND_OVER = 200                                        # 200 + e: t + e errors, e = 1 .. 3
+
 
 class Code:
     """RS(255, 255 - num_roots) over GF(2^8) / poly, generator roots alpha^(root_gap (first_root + i)), i < num_roots."""

@@ -20,10 +20,14 @@ device atomics and every kernel's arithmetic order is fixed), and the serial run
     at the bound of the kind's own GPU test for Deemp, ComplexAgc (exact recurrence) and CostasLoop (4 x the float loop's
     error); the PSK chains against the composition of the separate device handles, as tests/test_gpu_psk.py does; SsbDemod as the
     real part of the oracle's mixer; StereoFmDemod as its own test does, in three layers (fm_ref, the pilot FIR under the yardstick
-    rule, stereo_mix_ref of the handle's own pilot rows bit for bit), every call in the peak regime.
+    rule, stereo_mix_ref of the handle's own pilot rows bit for bit), every call in the peak regime;
+  * the forward error correction handles of qdsp_amd.fec (RsDecoder, FalconRs, and Deframer -> FalconRs through the deframer's
+    device counts): _rs_ref.Layout.decode under the maps in force -- set_maps switches the model's layout --, bit for bit over the
+    whole output buffer, the counts and the whole errs buffer, each filled with a sentinel by a copy queued in front of the call
+    (bytes behind a row's last good frame and errs entries behind a short row included); frames from test_gpu_rs.gen_frames.
 
 `test_control_*` proves that the hold holds and that a race shows; `test_scenarios_cover_the_library` (last) that every kernel
-family and every public setter / getter / reset / configure of qdsp_amd.ops was raced.  With ASYNC_ORDER_REPORT=<file> the measured
+family and every public setter / getter / reset / configure of qdsp_amd.ops and qdsp_amd.fec was raced.  With ASYNC_ORDER_REPORT=<file> the measured
 host times and the holds used go there (profiles/async_order_windows.txt is one such run)."""
 import ctypes as C
 import inspect
@@ -39,6 +43,7 @@ import _async as A  # noqa: E402
 import _deframer_ref as DF  # noqa: E402
 import _mmcr_ref as MM  # noqa: E402
 import _numerics as NU  # noqa: E402
+import _rs_ref as RS  # noqa: E402
 import oracle as O  # noqa: E402
 from _async import Call, H, Host  # noqa: E402
 from _psk_ref import delay_imag_ref  # noqa: E402
@@ -53,6 +58,7 @@ from test_ff_agc_cpu import ffagc_ref  # noqa: E402
 from test_gpu_fuzz import FAMILIES  # noqa: E402
 from test_gpu_handover import F_A, F_B, TOL_HEAD, TOL_HIST, TOL_PHASE, TOL_RMS, _plans, _steer  # noqa: E402
 from test_gpu_numerics import CHAN, CHAN_F, FAM, FAM_IDS, _os_layout, _pin, _taps  # noqa: E402
+from test_gpu_rs import Pool, gen_frames  # noqa: E402
 from test_gpu_stereo_fm import REGIME_GAP  # noqa: E402
 from test_level_cpu import ROW_TILES as LEVEL_ROW_TILES, TILE as LEVEL_TILE, agc_decay, agc_exact_decay, agc_ref, squelch_ref  # noqa: E402
 from test_stereo_fm_cpu import cfr_of, modulate, pilot_taps as sfm_pilot_taps, stereo_mix_ref  # noqa: E402
@@ -66,7 +72,7 @@ _SEEN = set()                      # kernel names of the async runs
 _RACED = set()                     # (class name, method) of every host action that ran with its window open
 PER_ROW_FAMILIES = {"fm_demod_kernel", "am_sub_kernel", "ssb_demod_kernel", "deemp_row_kernel", "deemp_scan_kernel", "level_row_kernel",
                     "level_apply_kernel", "stereo_mix_kernel", "ff_agc_kernel", "cagc_row_kernel", "cagc_scan_kernel", "costas_kernel",
-                    "mm_clock_kernel", "row_fir_kernel", "delay_imag_kernel", "threshold_kernel", "deframe_match_kernel"}
+                    "mm_clock_kernel", "row_fir_kernel", "delay_imag_kernel", "threshold_kernel", "deframe_match_kernel", "rs_decode_kernel"}
 DMA = {"fir_fft_dma_kernel", "fir_fft_dmapk_kernel"}     # members of the 4096-point overlap-save family (conftest.kname)
 OVERLAP_SAVE = DMA | {"fir_fft_kernel", "fir_fft1k_kernel", "pfb_dec8_kernel", "pfb_dec4_kernel", "pfb_dec8_real_kernel", "pfb_dec4_real_kernel"}
 DIRECT_FORMS = {"fir_core_kernel", "fir_lat_kernel", "decim_win_kernel", "decim_mfma_kernel", "decim_mfma_real_kernel", "resamp_lm_kernel",
@@ -883,16 +889,16 @@ class _MmModel(_CountedModel):
 
 
 class _DeframerModel(_CountedModel):
-    def __init__(self, rows, flt):
+    def __init__(self, rows, flt, frame=None, sync=None):
         super().__init__(rows)
-        self.flt, self.sync = flt, SYNC
+        self.flt, self.frame, self.sync = flt, FRAME if frame is None else frame, SYNC if sync is None else sync
         self.reset()
 
     def count_of(self, w):
         return len(w)
 
     def reset(self):
-        self.st = [DF.new_state(FRAME, len(SYNC)) for _ in range(self.rows)]
+        self.st = [DF.new_state(self.frame, len(self.sync)) for _ in range(self.rows)]
         self.last_counts = [0] * self.rows
 
     def set_sync(self, sync):
@@ -910,7 +916,7 @@ class _DeframerModel(_CountedModel):
         out = []
         for r in range(self.rows):
             row = x[r] if counts is None else x[r][:counts[r]]
-            frames, _, self.st[r] = DF.deframe_ref(DF.threshold_ref(row) if self.flt else row, FRAME, self.sync, self.st[r])
+            frames, _, self.st[r] = DF.deframe_ref(DF.threshold_ref(row) if self.flt else row, self.frame, self.sync, self.st[r])
             out.append(frames)
         self.last_counts = [len(f) for f in out]
         return out
@@ -1540,6 +1546,276 @@ def test_msk_to_deframer_count_handover(ops):
     _anchor(_three_ways("msk -> deframer", scenario))
 
 
+# ------------------------------------------------------------------------------------------------ forward error correction (qdsp_amd.fec)
+RS_SENT, RS_ESENT = 0xA5, -99
+FALCON_BITS = 1279 * 8
+FALCON_SYNC = np.unpackbits(np.array([0x1A, 0xCF, 0xFC, 0x1D], np.uint8))
+
+
+@pytest.fixture(scope="module")
+def fec(ops):
+    from qdsp_amd import fec as _fec
+
+    return _fec
+
+
+class _RsModel:
+    """_rs_ref.Layout.decode carried through the steps: set_maps changes the layout, every call is decoded under the one in force."""
+
+    def __init__(self, lay, rows):
+        self.lay, self.last_counts = lay, np.zeros(rows, np.int32)
+
+    def set_maps(self, in_map=None, out_map=None, xor=None):
+        self.lay = RS.Layout(self.lay.code, self.lay.depth, self.lay.skip, self.lay.full_out, in_map, out_map, xor)
+
+    def decode(self, frames):
+        frames = np.asarray(frames, np.uint8).reshape(-1, self.lay.frame_in)
+        if not len(frames):
+            return np.zeros((0, self.lay.frame_out), np.uint8), np.zeros((0, self.lay.depth), np.int32)
+        out, good, errs = self.lay.decode(frames)
+        return out[good], errs
+
+    def check(self, got, per_row, label):
+        """got: the whole output buffer (sentinel-filled before the call), the counts and the whole errs buffer (None: not asked
+        for); per_row: the frames every row's decoder took.  Every byte and every entry: good frames packed, sentinels behind."""
+        out, counts = got[0], got[1]
+        want, wc = np.full_like(out, RS_SENT), []
+        we = np.full_like(got[2], RS_ESENT) if len(got) > 2 else None
+        for r, frames in enumerate(per_row):
+            g, e = self.decode(frames)
+            want[r, :g.size] = g.ravel()
+            wc.append(len(g))
+            if we is not None:
+                we[r, :e.size] = e.ravel()
+        self.last_counts = np.asarray(wc, np.int32)
+        assert counts.tolist() == wc, f"{label}: counts {counts.tolist()} / the definition's {wc}"
+        assert A.same_bits(out, want), f"{label}: output buffer: {np.argwhere(out != want)[:4].tolist()}"
+        assert we is None or np.array_equal(got[2], we), f"{label}: errs: {np.argwhere(got[2] != we)[:4].tolist()}"
+
+    def same_counts(self, v):
+        assert np.array_equal(v[0], self.last_counts), ("counts", v[0], self.last_counts)
+
+
+def _rs_out(op, nframes, with_errs=True):
+    """A function that gives a fresh output buffer (7 bytes of slack per row) and errs buffer, each filled with its sentinel by a
+    copy queued on the current stream."""
+    import torch
+
+    osent = torch.full((op.nchan, nframes * op.frame_out + 7), RS_SENT, dtype=torch.uint8, device="cuda")
+    esent = torch.full((op.nchan, max(nframes * (op.frame_in // 255), 1)), RS_ESENT, dtype=torch.int32, device="cuda") if with_errs else None
+
+    def fresh():
+        out, errs = torch.empty_like(osent), None if esent is None else torch.empty_like(esent)
+        out.copy_(osent)
+        if errs is not None:
+            errs.copy_(esent)
+        return out, errs
+
+    return fresh
+
+
+def _rs_call(label, op, model, x, nframes, in_counts=None):
+    """op.process_batch over the rows x (rows, nframes * frame_in), per-row counts from a device tensor that is itself copied on the
+    current stream.  The value: the whole output buffer, the counts, the whole errs buffer."""
+    xin, fresh = _In(x, rows=True), _rs_out(op, nframes)
+    cin = None if in_counts is None else _In(np.asarray(in_counts, np.int32))
+    take = [nframes] * len(x) if in_counts is None else [min(max(int(c), 0), nframes) for c in in_counts]
+    per_row = [x[r, :take[r] * op.frame_in] for r in range(len(x))]
+
+    def fn():
+        out, errs = fresh()
+        _, counts = op.process_batch(xin(), out, nframes=nframes, in_counts=None if cin is None else cin(), errs=errs)
+        return out, counts, errs
+
+    return _checked(Call(label, fn, op, {"rs_decode_kernel"}), lambda v: model.check(v, per_row, label))
+
+
+class _Feed:
+    """The frames of a pool dealt out in order: `rows` rows of n frames each, as a (rows, n * frame_in) array."""
+
+    def __init__(self, frames):
+        self.frames, self.at = frames, 0
+
+    def __call__(self, rows, n, through=None):
+        assert self.at + rows * n <= len(self.frames)
+        x = self.frames[self.at:self.at + rows * n].reshape(rows, -1)
+        self.at += rows * n
+        return np.ascontiguousarray(x if through is None else through[x])
+
+
+def test_falcon_rs(ops, fec):
+    """FalconRs over 5 rows, scratch for 2 frames a row: a 7-frame call (the scratch is freed and reallocated at call time) and
+    the same again; set_maps with another output permutation and XOR sequence; counts; per-row counts from a device tensor (0,
+    all, more than there are, negative); a 12-frame call while two calls on the scratch it frees are still queued; set_maps back
+    to the identity (the frames then come in the decoder's own domain).  A call that drains the queue is followed by one that
+    does not, so that every host action finds a library call queued."""
+    lay = RS.falcon_layout()
+    rng = np.random.default_rng(41)
+    pool = Pool(lay, gen_frames(rng, lay, ROWS * 64))
+    assert 0.5 < pool.good.mean() < 0.9 and pool.errs.max() == 8
+    out_map, xor = rng.permutation(256).astype(np.uint8), rng.integers(0, 256, 100).astype(np.uint8)
+
+    def scenario():
+        op = fec.FalconRs(nchan=ROWS, max_block=2)
+        model, feed = _RsModel(lay, ROWS), _Feed(pool.frames)
+        steps = []
+
+        def call(n, in_counts=None, through=None):
+            steps.append(_rs_call(f"process_batch {len(steps)} ({n})", op, model, feed(ROWS, n, through), n, in_counts))
+
+        call(7)                                        # larger than any call before: rs_scratch frees and reallocates
+        call(7)
+        steps.append(_checked(H(op, "set_maps", lay.in_map, out_map, xor), lambda v: model.set_maps(lay.in_map, out_map, xor)))
+        call(4)
+        call(4)
+        steps.append(_checked(H(op, "counts"), model.same_counts))
+        call(5)
+        call(7, in_counts=[0, 7, 10, -2, 3])
+        call(12)                                       # the second regrowth, the two calls before it still queued
+        call(12)
+        steps.append(_checked(H(op, "set_maps"), lambda v: model.set_maps()))
+        call(6, through=lay.in_map)
+        return steps
+
+    _anchor(_three_ways("fec FalconRs", scenario))
+
+
+def test_rs_decoder_one_row(ops, fec):
+    """RsDecoder with one row, three codewords of RS(255, 251) to a frame behind two skipped bytes, scratch for 4 frames: the
+    1-D tensor form (launch on the caller's stream, then its own download of the count: it drains the queue, so a process_batch
+    call on a (1, n) view goes in front of each and behind it), counts, set_maps, and time_dev (its two calls into one
+    sentinel-filled buffer; the time itself is dropped), each with a call still queued."""
+    code = RS.Code(0x11d, 1, 1, 4)
+    rng = np.random.default_rng(42)
+    in_map, out_map = rng.permutation(256).astype(np.uint8), rng.permutation(256).astype(np.uint8)
+    xor = rng.integers(0, 256, 300).astype(np.uint8)
+    lay_a, lay_b = RS.Layout(code, 3, 2, 0), RS.Layout(code, 3, 2, 0, in_map, out_map, xor)
+    pool_a, pool_b = (Pool(lay, gen_frames(rng, lay, 32, p_bad=0.35)) for lay in (lay_a, lay_b))
+    assert all(0 < p.good.sum() < 32 and p.errs.max() == 2 for p in (pool_a, pool_b))
+
+    def scenario():
+        op = fec.RsDecoder(0x11d, 1, 1, 4, depth=3, skip=2, nchan=1, max_block=4)
+        model = _RsModel(lay_a, 1)
+        feed = {"f": _Feed(pool_a.frames)}
+        steps = []
+
+        def batch(n):
+            steps.append(_rs_call(f"process_batch {len(steps)} ({n})", op, model, feed["f"](1, n), n))
+
+        def one_d(n):
+            x = feed["f"](1, n)[0]
+            xin = _In(x)
+            label = f"process {len(steps)} ({n})"
+
+            def chk(v):
+                want, _ = model.decode(x)
+                model.last_counts = np.asarray([len(want)], np.int32)
+                assert A.same_bits(v[0], want), f"{label}: not the definition's good frames"
+            steps.append(_checked(Call(label, lambda: op.process(xin()), op, {"rs_decode_kernel"}), chk))
+
+        def timed(n):
+            x = feed["f"](1, n)
+            xin, fresh = _In(x, rows=True), _rs_out(op, n, with_errs=False)
+
+            def fn():
+                out, _ = fresh()
+                assert op.time_dev(xin(), out, 2) >= 0.0
+                return out, op.counts()
+            steps.append(_checked(Host("RsDecoder.time_dev", fn, op, "time_dev"), lambda v: model.check(v, [x[0]], "time_dev")))
+
+        batch(3)
+        one_d(6)                                       # past max_block: the scratch grows
+        batch(4)
+        one_d(5)
+        batch(2)
+        steps.append(_checked(H(op, "counts"), model.same_counts))
+        batch(4)
+
+        def to_b(v):
+            model.set_maps(in_map, out_map, xor)
+        steps.append(_checked(H(op, "set_maps", in_map, out_map, xor), to_b))
+        feed_b = _Feed(pool_b.frames)
+        feed["f"] = feed_b
+        batch(3)
+        timed(4)
+        batch(2)
+        return steps
+
+    _anchor(_three_ways("fec RsDecoder", scenario))
+
+
+def test_deframer_to_falcon_rs_count_handover(ops, fec):
+    """Deframer.process_batch(bits) -> FalconRs.process_batch(frames, nframes = the deframer's capacity, in_counts = its device
+    counts) on one stream with no host step in between; Deframer.set_state (the next call starts a frame in the middle of one,
+    which the decoder drops), FalconRs.set_maps and counts with a pair still queued.  Falcon frames with the real sync word back
+    to back behind a short gap, a call boundary every 2.39 frames, so that one frame straddles every boundary.  Reference:
+    deframe_ref carried over the calls, then Layout.decode over each row's frames."""
+    import torch
+
+    lay = RS.falcon_layout()
+    rng = np.random.default_rng(43)
+    npair, n = 7, 2 * FALCON_BITS + 4000
+    per_row = -(-npair * n // FALCON_BITS) + 1
+    frames = gen_frames(rng, lay, ROWS * per_row, p_bad=0.3)
+    frames[:, :4] = [0x1A, 0xCF, 0xFC, 0x1D]
+    pool = Pool(lay, frames)
+    assert 0.4 < pool.good.mean() < 0.9
+    bits = np.zeros((ROWS, npair * n), np.uint8)
+    for r in range(ROWS):
+        gap = int(rng.integers(0, 300))
+        assert all((j * n - gap) % FALCON_BITS for j in range(1, npair))          # a frame straddles every call boundary
+        row = np.concatenate([rng.integers(0, 2, gap).astype(np.uint8), np.unpackbits(frames[r * per_row:(r + 1) * per_row].ravel())])
+        bits[r] = row[:npair * n]
+    out_map, xor = rng.permutation(256).astype(np.uint8), rng.integers(0, 256, 100).astype(np.uint8)
+
+    def scenario():
+        dfr = ops.Deframer(FALCON_BITS, FALCON_SYNC, 0, nchan=ROWS, max_block=0)
+        cap = dfr.out_size(n)
+        rs = fec.FalconRs(nchan=ROWS, max_block=cap)
+        dref, rref = _DeframerModel(ROWS, False, FALCON_BITS, FALCON_SYNC), _RsModel(lay, ROWS)
+        fresh = _rs_out(rs, cap)
+        steps, last, want, at = [], {}, {}, [0]
+
+        def pair():
+            x = np.ascontiguousarray(bits[:, at[0]:at[0] + n])
+            at[0] += n
+            xd = _In(x, rows=True)
+
+            def run_dfr():
+                out = torch.zeros((ROWS, cap * dfr.frame_bytes), dtype=torch.uint8, device="cuda")
+                last["frames"], last["counts"] = dfr.process_batch(xd(), out=out)
+                return last["frames"], last["counts"]
+
+            def run_rs():
+                out, errs = fresh()
+                _, counts = rs.process_batch(last["frames"], out, nframes=cap, in_counts=last["counts"], errs=errs)
+                return out, counts, errs
+
+            def chk_dfr(v):
+                want["frames"] = dref.process(x)
+                _check_counted("deframer", v, want["frames"])
+            steps.append(_checked(Call(f"deframer {len(steps)}", run_dfr, dfr, {"deframe_match_kernel"}), chk_dfr))
+            steps.append(_checked(Call(f"rs {len(steps)}", run_rs, rs, {"rs_decode_kernel"}), lambda v: rref.check(v, want["frames"], "rs")))
+
+        pair()
+        pair()
+        steps.append(_checked(H(dfr, "set_state", 0, 4, False, -1), lambda v: dref.set_state(0, 4, False, -1)))
+        pair()                                         # (frames cut from the middle of others, all dropped; then it searches again)
+        pair()
+        steps.append(_checked(H(rs, "set_maps", lay.in_map, out_map, xor), lambda v: rref.set_maps(lay.in_map, out_map, xor)))
+        pair()
+        pair()
+        steps.append(_checked(H(rs, "counts"), rref.same_counts))
+        pair()
+        return steps
+
+    serial = _three_ways("deframer -> FalconRs", scenario)
+    _anchor(serial)
+    good = sum(int(v[1].sum()) for (_, v), st in zip(serial.outputs, serial.steps) if st.label.startswith("rs "))
+    taken = sum(int(v[1].sum()) for (_, v), st in zip(serial.outputs, serial.steps) if st.label.startswith("deframer "))
+    assert 0 < good < taken, (good, taken)
+
+
 # ------------------------------------------------------------------------------------------------ Math, Xlator alone, the sine source
 def test_math_xlator_and_sine_source(ops):
     from qdsp_amd import capi
@@ -1619,10 +1895,11 @@ def test_math_xlator_and_sine_source(ops):
 
 
 # ------------------------------------------------------------------------------------------------ release
-@pytest.mark.parametrize("which", ["engine", "per_row", "chain"])
+@pytest.mark.parametrize("which", ["engine", "per_row", "chain", "fec"])
 def test_close_while_the_last_call_is_held(ops, monkeypatch, which):
     """process into a torch-owned output, then close() while that call is still queued: every *_destroy waits for the device
-    before its first hipFree (Engine destroy, level_free, chain_free and the stages' own), so the output is the serial run's."""
+    before its first hipFree (Engine destroy, level_free, chain_free and the stages' own, rs_free), so the output is the serial
+    run's."""
     _pin(monkeypatch, {})
 
     def scenario():
@@ -1639,6 +1916,14 @@ def test_close_while_the_last_call_is_held(ops, monkeypatch, which):
             xs = [_In(_cx(rng, ROWS, 3 * TILE + 5), rows=True) for _ in range(2)]
             outs = [torch.zeros((ROWS, 3 * TILE + 5), dtype=torch.complex64, device="cuda") for _ in xs]
             call = lambda i: op.process_batch(xs[i](), outs[i])                                        # noqa: E731
+        elif which == "fec":
+            from qdsp_amd import fec
+
+            lay = RS.falcon_layout()
+            op = fec.FalconRs(nchan=ROWS, max_block=3)
+            xs = [_In(gen_frames(rng, lay, ROWS * 3).reshape(ROWS, -1), rows=True) for _ in range(2)]
+            outs = [torch.zeros((ROWS, 3 * op.frame_out), dtype=torch.uint8, device="cuda") for _ in xs]
+            call = lambda i: op.process_batch(xs[i](), outs[i])                                        # noqa: E731
         else:
             op = ops.MskDemod(48000.0, 6000.0, 12000.0, nchan=ROWS, max_block=0)
             xs = [_In(_cx(rng, ROWS, 4111, 0.05), rows=True) for _ in range(2)]
@@ -1654,20 +1939,27 @@ NOT_RACED = {
     ("*", "set_done_event"): "only read by process_ex's deferred link, i.e. on the handle's own or the library's shared stream: out of this module's reach",
     ("*", "set_history_ptr"): "the raw-pointer spelling of set_history_dev (same C entry point, which is raced), for the C ring",
     ("Threshold", "reset"): "Threshold has no state: the method does nothing",
+    ("RsDecoder", "reset"): "no state between frames: the method does nothing",
+    ("FalconRs", "reset"): "no state between frames: the method does nothing",
 }
 
 
 def test_scenarios_cover_the_library(ops):
     """Every kernel family of tests/test_gpu_fuzz.py's FAMILIES and every per-row kernel family ran in an async scenario, and every
-    public setter, getter, reset and configure of every operator class was a racing host action (or is excluded above, with a reason)."""
+    public setter, getter, reset and configure of every operator class of qdsp_amd.ops and qdsp_amd.fec was a racing host action
+    (or is excluded above, with a reason)."""
+    from qdsp_amd import fec
+
     seen = set(_SEEN)
     if seen & DMA:
         seen.add("fir_fft_dma_kernel")
     missing = (FAMILIES | PER_ROW_FAMILIES) - seen
     assert not missing, f"kernel families no async scenario ran: {sorted(missing)} (seen: {sorted(seen)})"
     unraced, public, raced_methods = [], set(), set()
-    for name, cls in inspect.getmembers(ops, inspect.isclass):
-        if cls.__module__ != ops.__name__ or name.startswith("_"):
+    classes = [(n, c, m) for m in (ops, fec) for n, c in inspect.getmembers(m, inspect.isclass)]
+    assert {"RsDecoder", "FalconRs"} <= {n for n, c, m in classes if c.__module__ == fec.__name__}
+    for name, cls, mod in classes:
+        if cls.__module__ != mod.__name__ or name.startswith("_"):
             continue
         for m in dir(cls):
             if not (m.startswith("set_") or m.startswith("get_") or m in ("reset", "configure", "advance")) or not callable(getattr(cls, m)):

@@ -1,9 +1,11 @@
 """Threshold and Deframer on the GPU against their numpy definition (tests/_deframer_ref.py), bit for bit: frames, per-call counts
 and the state read back, with sentinel bytes around every output row and behind each row's last frame; shapes around the kernels'
 boundaries, call cuts, the state machine's corners, input bytes other than 0 / 1, batches with per-row counts, float rows, the
-MSK chain feeding the deframer on one stream, Threshold alone, and the link codes.
+MSK chain feeding the deframer on one stream, Threshold alone, the link codes, and the C++ mirror's frame_check on the real library.
 """
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -647,3 +649,54 @@ def test_threshold_process_ex_links(torch):
     for il, ol in ((HOSTL, 4), (HOSTL, -1), (DEFER, HOSTL), (-1, HOSTL)):
         assert L_.qdsp_hip_threshold_process_ex(fresh._h, x.ctypes.data, il, 10, y.ctypes.data, ol) == EINVAL, (il, ol)
     L_.qdsp_hip_event_destroy(ev)
+
+
+# ---- the C++ mirror ------------------------------------------------------------------------------------------------------------------
+HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "qdsp_amd", "host")
+BIN = os.path.join(HOST, "build", "frame_check")
+
+
+@pytest.fixture(scope="module")
+def harness():
+    if not os.path.exists(BIN):
+        subprocess.check_call(["make", "-C", HOST, "build/frame_check"], stdout=subprocess.DEVNULL, timeout=300)
+    return BIN
+
+
+@pytest.fixture(scope="module")
+def mirror_streams():
+    """The streams of tests/test_deframer_cpu.py's run of the harness on the fake library: a random 32-bit sync word, then per frame
+    length 6000 bits and their soft symbols, and what the bit-by-bit definition cuts from them (computed once)."""
+    rng = np.random.default_rng(5)
+    sync = rng.integers(0, 2, 32).astype(np.uint8)
+    out = {"sync": sync}
+    for fl in (256, 9):
+        x = D.stream_with_frames(rng, 6000, fl, sync, gap=(0, 200), p_sync=0.7)
+        soft_x = np.where(x > 0, 1.0, -1.0).astype(np.float32) * rng.uniform(0.1, 2.0, len(x)).astype(np.float32)
+        want, _, _ = D.deframe_bits(x, fl, sync)
+        assert len(want) >= 5
+        out[fl] = (x, soft_x, want)
+    return out
+
+
+@pytest.mark.parametrize("block", [4096, 33, 5])
+@pytest.mark.parametrize("fl", [256, 9])
+@pytest.mark.parametrize("kind,link", [("b", "host"), ("f", "dev"), ("f", "host")])
+def test_frame_check_files_are_the_operators(torch, harness, mirror_streams, tmp_path, kind, link, fl, block):
+    """source -> [Threshold ->] Deframer -> sink of the C++ mirror on the real library, the Threshold's output handed over in device
+    memory or through the host buffers: the file is what one Deframer handle gives over the same blocks, and the definition's."""
+    sync = mirror_streams["sync"]
+    x, soft_x, want = mirror_streams[fl]
+    src = soft_x if kind == "f" else x
+    sync.tofile(tmp_path / "sync.u8")
+    src.tofile(tmp_path / "x.bin")
+    p = subprocess.run([harness, kind, link, "x.bin", "y.bin", str(block), str(fl), "sync.u8"], cwd=tmp_path, check=True, timeout=180,
+                       capture_output=True, text=True)
+    assert "graph ok" in p.stdout and f"{link} link" in p.stdout, p.stdout
+    got = np.fromfile(tmp_path / "y.bin", dtype=np.uint8)
+    op = ops.Deframer(fl, sync, 1 if kind == "f" else 0, max_block=block)
+    mine = [op.process(src[a:a + block]) for a in range(0, len(src), block)]
+    mine = np.concatenate(mine)
+    assert len(want) >= 5 and mine.shape == want.shape
+    assert got.tobytes() == mine.tobytes(), "the mirror's file is not the operator's frames"
+    assert got.tobytes() == want.tobytes(), "the mirror's file is not the definition's frames"

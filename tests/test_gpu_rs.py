@@ -1,9 +1,12 @@
-"""The Reed-Solomon decoder and FalconRS on the GPU against the numpy definition (tests/_rs_ref.py) and the recording of libcorrect's
-own answers (tests/golden/rs_ref_io.npz), bit for bit: output bytes with sentinels around every row and behind each row's last good
-frame, the per-row counts and the per-codeword error counts with sentinels behind a short row.
+"""The Reed-Solomon decoder and FalconRS on the GPU against the numpy definition (tests/_rs_ref.py) and the recordings of libcorrect's
+own answers (tests/golden/rs_ref_io.npz, rs_ref_codes.npz), bit for bit: output bytes with sentinels around every row and behind each
+row's last good frame, the per-row counts and the per-codeword error counts with sentinels behind a short row; and the C++ mirror's
+falcon_check on the real library.
 """
 import ctypes as C
 import os
+import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +18,8 @@ from qdsp_amd import capi, fec, ops
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+HOST = os.path.join(os.path.dirname(HERE), "qdsp_amd", "host")
+BIN = os.path.join(HOST, "build", "falcon_check")
 EINVAL, ESIZE = -10001, -10003
 SENT, ESENT = 0xA5, -99
 HOSTL, DEVL, PIPE, DEFER = 0, 1, 2, 3
@@ -32,6 +37,11 @@ def torch():
 @pytest.fixture(scope="module")
 def golden():
     return np.load(os.path.join(HERE, "golden", "rs_ref_io.npz"))
+
+
+@pytest.fixture(scope="module")
+def codes():
+    return np.load(os.path.join(HERE, "golden", "rs_ref_codes.npz"))
 
 
 def dev(torch, x):
@@ -114,9 +124,12 @@ def call(torch, d, pool, idx, nframes, in_counts=None, in_pad=5, out_pad=7, lead
 
 # ---- 1. every recorded word ----------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("ci", range(3))
-def test_every_recorded_word(torch, golden, ci):
-    """The words libcorrect answered for, as frames of depth 1: message bytes, verdict and the order its locator search left."""
+@pytest.mark.parametrize("ci", range(3 + len(R.ODD_CODES)))
+def test_every_recorded_word(torch, golden, codes, ci):
+    """The words libcorrect answered for, as frames of depth 1: message bytes, verdict and the order its locator search left.
+    0 .. 2: the three codes of rs_ref_io.npz; from 3 on: the codes of rs_ref_codes.npz (R.ODD_CODES)."""
+    if ci >= 3:
+        golden, ci = codes, ci - 3
     p = tuple(int(v) for v in golden[f"params_{ci}"])
     words, rc, order, msg = golden[f"words_{ci}"], golden[f"rc_{ci}"], golden[f"order_{ci}"], golden[f"msg_{ci}"]
     k = 255 - p[3]
@@ -230,6 +243,35 @@ def test_scan_past_its_step_of_256_frames(torch):
     call(torch, d, pool, [np.arange(257), np.arange(300, 557)], 257, in_counts=[255, 257])
 
 
+@pytest.mark.parametrize("params", R.ODD_CODES, ids=lambda p: "%x-%d-%d-%d" % p)
+def test_codes_off_the_dword_grid(torch, params):
+    """num_roots that are no multiple of the four syndromes of a dword, the smallest and the largest the kernel takes, first roots
+    0 and 255 and gaps 2, 7 and 254 (tests/test_rs_cpu.py holds the definition to libcorrect's recorded answers for these codes).
+    From five roots on: depths 1, 3 and 8 over pools of 24 frames, maps and an XOR sequence, per-row counts.  With 2 and 3 roots
+    nearly every word beyond t is taken to another codeword, not refused: depth 1 and 1200 frames, nine in ten of them beyond t."""
+    nr = params[3]
+    rng = np.random.default_rng(7000 + nr)
+    if nr < 5:
+        lay = R.Layout(R.Code(*params), 1, 0, 0)
+        pool = Pool(lay, gen_frames(rng, lay, 1200, p_bad=0.9))
+        used = np.r_[0:600, 600:1113]
+        assert (~pool.good[used]).sum() >= 4 and pool.good[used].sum() >= 500 and pool.errs.max() >= nr // 2
+        d = fec.RsDecoder(*params, nchan=2, max_block=16)
+        call(torch, d, pool, [np.arange(600), np.arange(600, 1200)], 600, in_counts=[600, 513])
+        assert d.last_kernel()["block"] == 64
+        return
+    for depth, skip, full_out in ((1, 0, 0), (3, 5, 1), (8, 2, 0)):
+        in_map, out_map = rng.permutation(256).astype(np.uint8), rng.permutation(256).astype(np.uint8)
+        xor = rng.integers(0, 256, int(rng.integers(1, 255 * depth + 1))).astype(np.uint8)
+        lay = R.Layout(R.Code(*params), depth, skip, full_out, in_map, out_map, xor)
+        pool = Pool(lay, gen_frames(rng, lay, 24, p_bad=0.35))
+        used = np.r_[0:8, 8:13, 16:23]
+        assert pool.good[used].sum() >= 2 and (~pool.good[used]).sum() >= 2 and pool.errs.max() >= nr // 2
+        d = fec.RsDecoder(*params, depth=depth, skip=skip, full_out=full_out, in_map=in_map, out_map=out_map, xor=xor, nchan=3, max_block=8)
+        call(torch, d, pool, [np.arange(8), np.arange(8, 16), np.arange(16, 24)], 8, in_counts=[8, 5, 7], lead=depth, olead=depth + 2)
+        assert d.last_kernel()["block"] == 64 * depth
+
+
 def test_frames_of_all_zeros_and_all_ones(torch):
     lay = R.falcon_layout()
     frames = np.zeros((4, 1279), np.uint8)
@@ -334,6 +376,48 @@ def test_entry_forms_give_the_same_bytes(torch, falcon):
         if out_link == DEVL:
             assert (res[want.size:] == SENT).all()
     assert d.process_ex(hin.ctypes.data, HOSTL, 0, 0, HOSTL) == 0
+
+
+@pytest.fixture(scope="module")
+def harness():
+    if not os.path.exists(BIN):
+        subprocess.check_call(["make", "-C", HOST, "build/falcon_check"], stdout=subprocess.DEVNULL, timeout=300)
+    return BIN
+
+
+@pytest.fixture(scope="module")
+def mirror_frames(golden):
+    """The input of tests/test_rs_cpu.py's run of the harness on the fake library: the recording's ten frames, then twelve with a
+    table of error counts per codeword; what the definition makes of them, computed once."""
+    lay = R.falcon_layout()
+    rng = np.random.default_rng(6)
+    frames = lay.encode(rng.integers(0, 256, (12, 5, lay.code.k)).astype(np.uint8))
+    for f in range(12):
+        for c in range(5):
+            ne = [0, 1, 8, 3, 9, 0, 12, 5, 8, 2, 0, 7][(f + 3 * c) % 12] if f % 4 else (f + c) % 9
+            frames[f, 4 + rng.choice(255, ne, replace=False) * 5 + c] ^= rng.integers(1, 256, ne).astype(np.uint8)
+    frames = np.concatenate([golden["frames"], frames])
+    want, good, _ = lay.decode(frames)
+    assert 5 <= good.sum() < len(frames)
+    return frames, want[good]
+
+
+@pytest.mark.parametrize("per", [1, 3, 22])
+@pytest.mark.parametrize("link", ["dev", "host"])
+def test_falcon_check_files_are_the_operator(torch, harness, mirror_frames, tmp_path, link, per):
+    """source -> FalconRS -> sink of the C++ mirror on the real library, the blocks handed over in device memory or in the host
+    buffers, `per` frames to a block: the file is FalconRs.process over the same blocks, and the definition's good frames."""
+    frames, want = mirror_frames
+    frames.tofile(tmp_path / "x.u8")
+    p = subprocess.run([harness, link, "x.u8", "y.bin", str(per)], cwd=tmp_path, check=True, timeout=180, capture_output=True, text=True)
+    assert "graph ok" in p.stdout and f"{link} link" in p.stdout, p.stdout
+    in_dev = int(re.search(r"\((\d+) in device memory\)", p.stdout).group(1))
+    assert (in_dev > 0) == (link == "dev"), p.stdout
+    got = np.fromfile(tmp_path / "y.bin", dtype=np.uint8)
+    d = fec.FalconRs(nchan=1, max_block=per)
+    mine = np.concatenate([d.process(frames[a:a + per]) for a in range(0, len(frames), per)])
+    assert got.tobytes() == mine.tobytes(), "the mirror's file is not the operator's frames"
+    assert got.tobytes() == want.tobytes(), "the mirror's file is not the definition's good frames"
 
 
 def test_error_codes(torch, falcon):

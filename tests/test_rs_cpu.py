@@ -1,5 +1,6 @@
 """The Reed-Solomon decoder and FalconRS without a GPU: the numpy definition the GPU tests compare against (tests/_rs_ref.py)
-against a recording of libcorrect's own answers, the two CCSDS tables from their closed forms, the frame layout, the library's
+against two recordings of libcorrect's own answers (three codes with multiples of four roots; eight with 2 .. 31 roots off that grid,
+first roots 0 and 255 and other gaps), the two CCSDS tables from their closed forms, the frame layout, the library's
 surface and parameter errors, fec.py's argument checks, and the C++ mirror's harness on a fake library, plain and under the
 sanitizers.
 """
@@ -90,6 +91,65 @@ def test_the_recording_covers_the_stated_patterns(golden, ci):
     mis = good & (kind < 400) & (msg != sent).any(axis=1)          # ... that libcorrect takes to another codeword
     assert mis.sum() >= 8 and (kind[mis] > 200).all()
     assert (kind == 400).sum() == 2 and len(words) <= 120
+
+
+@pytest.fixture(scope="module")
+def codes():
+    return np.load(os.path.join(HERE, "golden", "rs_ref_codes.npz"))
+
+
+@pytest.mark.parametrize("ci", range(len(R.ODD_CODES)))
+def test_definition_equals_the_recording_of_the_odd_codes(codes, ci):
+    """tests/golden/rs_ref_codes.npz: libcorrect's answers for R.ODD_CODES -- num_roots 2, 3, 5, 6, 7, 10, 30 and 31, first roots 0
+    and 255, gaps 2, 7 and 254 -- recorded by tests/golden/make_rs_codes.py through oracle/_ref/librs_ref.so (make -C oracle rs_ref)."""
+    p = codes[f"params_{ci}"]
+    assert tuple(int(v) for v in p) == R.ODD_CODES[ci]
+    code = R.Code(*p)
+    words, rc, order, msg = codes[f"words_{ci}"], codes[f"rc_{ci}"], codes[f"order_{ci}"], codes[f"msg_{ci}"]
+    assert words.shape[1] == 255 and msg.shape == (len(words), code.k) and set(np.unique(rc).tolist()) <= {-1, code.k}
+    m, ok, o = R.decode(code, words)
+    assert np.array_equal(ok, rc >= 0), np.nonzero(ok != (rc >= 0))
+    assert np.array_equal(o, order), np.nonzero(o != order)
+    assert np.array_equal(m[ok], msg[ok])
+
+
+@pytest.mark.parametrize("ci", range(len(R.ODD_CODES)))
+def test_the_odd_codes_recording_covers_the_stated_places(codes, ci):
+    code = R.Code(*codes[f"params_{ci}"])
+    nr, t, k = code.num_roots, code.num_roots // 2, code.k
+    words, sent, kind, rc, order, msg = (codes[f"{n}_{ci}"] for n in ("words", "sent", "kind", "rc", "order", "msg"))
+    assert len(words) <= 64 and np.array_equal(code.encode(sent)[:, :k], sent)
+    diff = words != code.encode(sent)                               # the definition's encoder is libcorrect's: where the errors are
+    nerr, good = diff.sum(axis=1), rc >= 0
+    within = kind < R.KIND_OVER
+    assert (nerr[within] <= t).all() and good[within].all() and np.array_equal(msg[within], sent[within])
+    assert np.array_equal(order[within], nerr[within])
+    for e in range(t + 1):                                         # 0 .. t errors at random places
+        assert ((kind == e) & (nerr == e)).sum() >= 2, e
+    ends = kind == R.KIND_ENDS
+    assert diff[ends][:, 0].any() and diff[ends][:, 254].any() and (t < 2 or (diff[ends][:, 0] & diff[ends][:, 254]).any())
+    par = kind == R.KIND_PARITY
+    assert par.sum() >= 2 and not diff[par][:, :k].any() and nerr[par].min() >= 1 and nerr[par].max() == t
+    l63 = kind == R.KIND_LANE63                                     # coefficients 252 .. 254 are bytes 2, 1, 0
+    assert l63.sum() >= 2 and (nerr[l63] == t).all() and (diff[l63][:, :3].sum(axis=1) == min(t, 3)).all()
+    inv = np.zeros(255, np.int64)                                  # coefficient -> the locator's root for an error there
+    inv[code.loc[1:]] = np.arange(1, 256)
+    for b, kd in R.KIND_STRADDLE.items():
+        sel = np.flatnonzero(kind == kd)
+        assert len(sel) >= 2
+        roots = [np.sort(inv[254 - np.flatnonzero(diff[i])]) for i in sel]
+        assert all(len(r) == t and r.max() - r.min() == t - 1 for r in roots), roots       # t neighbours ...
+        assert any(b - 1 in r for r in roots) and any(b in r for r in roots)               # ... of the cut,
+        assert t < 2 or all(b - 1 in r and b in r for r in roots)                          # on both sides of it
+    over = kind > R.KIND_OVER
+    assert set(np.unique(kind[over] - R.KIND_OVER).tolist()) <= {1, 2, 3} and np.array_equal(nerr[over], t + kind[over] - R.KIND_OVER)
+    mis = good & over & (msg != sent).any(axis=1)
+    assert (~good[over]).sum() >= 4 and (nr >= 10 or mis.sum() >= 4), ((~good[over]).sum(), mis.sum())    # (rare from 10 roots on)
+    assert not (good & over & ~mis).any()                          # (no word beyond t comes back as sent)
+    # a miscorrection is another codeword, `order` places away: at most t, or with an odd number of roots, where the locator search
+    # takes one step more and may grow once more, (num_roots + 1) / 2
+    dist = (code.encode(msg[mis]) != words[mis]).sum(axis=1)
+    assert (dist <= (nr + 1) // 2).all() and np.array_equal(order[mis], dist)
 
 
 def test_miscorrected_words_come_out_as_the_other_codeword(golden):
