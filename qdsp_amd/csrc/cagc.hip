@@ -209,13 +209,7 @@ namespace qh {
 namespace {
 
 void cagc_free(Cagc* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par, (void*)d->d_part})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_state[0], d->d_state[1], d->d_par, d->d_part}); });
 }
 
 int cagc_fill_state(Cagc* d, int chan, double gain, bool both) {
@@ -277,11 +271,8 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_cagc_create(void** h, int device, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Cagc* d = new (std::nothrow) Cagc();
-    if (!d) return QDSP_HIP_ENOMEM;
-    d->launch = launch_as<Cagc, cagc_launch>;
+    Cagc* d = nullptr;
+    if (const int rc = op_new<Cagc, cagc_launch>(&d, h, true, device, nchan, max_block)) return rc;
     d->par.resize((size_t)nchan * 3);
     for (int c = 0; c < nchan; c++) {   // the reference's defaults (processing.h:291-294)
         d->par[3 * c] = 1.0f;
@@ -297,15 +288,10 @@ int qdsp_hip_cagc_create(void** h, int device, int nchan, int max_block) {
     if (err == hipSuccess) err = hipMalloc(&d->d_par, d->par.size() * sizeof(float));
     if (err == hipSuccess) err = hipMemcpy(d->d_par, d->par.data(), d->par.size() * sizeof(float), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMalloc(&d->d_part, (size_t)nchan * qk::kAmMaxParts * qk::kCagcPart * sizeof(double));
-    if (err != hipSuccess) {
-        cagc_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<cagc_free>(h, d, err);
 }
 int qdsp_hip_cagc_set(void* h, int chan, float set_point, float max_gain, float rate) {
-    Cagc* d = as_cagc(h);
+    Cagc* d = as<Cagc>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (std::isnan(set_point) || std::isnan(max_gain) || std::isnan(rate)) return QDSP_HIP_EINVAL;
     for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
@@ -316,35 +302,32 @@ int qdsp_hip_cagc_set(void* h, int chan, float set_point, float max_gain, float 
     return sync_upload(d, d->d_par, d->par.data(), d->par.size() * sizeof(float));
 }
 int qdsp_hip_cagc_get_gain(void* h, int chan, double* gain) {
-    Cagc* d = as_cagc(h);
+    Cagc* d = as<Cagc>(h);
     if (!d || !chan_ok(d, chan) || !gain) return QDSP_HIP_EINVAL;
     return sync_download(d, gain, d->d_state[d->cur] + chan, sizeof(double));
 }
 int qdsp_hip_cagc_set_gain(void* h, int chan, double gain) {
-    Cagc* d = as_cagc(h);
+    Cagc* d = as<Cagc>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     return cagc_fill_state(d, chan, gain, false);
 }
 int qdsp_hip_cagc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Cagc* d = as_cagc(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Cagc>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_cagc_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_cagc_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_cagc_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Cagc* d = as_cagc(h);
-    return d ? cagc_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Cagc, cagc_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_cagc_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                     void* hip_stream) {
-    Cagc* d = as_cagc(h);
-    return d ? cagc_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<Cagc, cagc_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_cagc_reset(void* h) {
-    Cagc* d = as_cagc(h);
+    Cagc* d = as<Cagc>(h);
     return d ? cagc_fill_state(d, -1, 1.0, true) : QDSP_HIP_EINVAL;
 }
-void qdsp_hip_cagc_destroy(void* h) { cagc_free(as_cagc(h)); }
+void qdsp_hip_cagc_destroy(void* h) { cagc_free(as<Cagc>(h)); }
 
 }  // extern "C"

@@ -58,16 +58,12 @@ struct CagcArgs {
 namespace qh {
 
 struct Cagc : StreamOp {
-    Cagc() : StreamOp(kCagcMagic) {}
+    static constexpr OpKind kKind = OpKind::Cagc;
     double* d_state[2] = {nullptr, nullptr};
     int cur = 0;
     float* d_par = nullptr;
     std::vector<float> par;                // [nchan][3]
     double* d_part = nullptr;
 };
-inline Cagc* as_cagc(void* h) {
-    Cagc* d = static_cast<Cagc*>(h);
-    return (d && d->magic == kCagcMagic) ? d : nullptr;
-}
 
 }  // namespace qh

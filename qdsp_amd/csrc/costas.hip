@@ -197,13 +197,7 @@ bool costas_gains(float bw, float* alpha, float* beta) {
 }
 
 void costas_free(Costas* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_state[0], d->d_state[1], d->d_par}); });
 }
 
 int costas_fill_state(Costas* d, int chan, double freq, double phase, bool both) {
@@ -257,13 +251,9 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_costas_create(void** h, int device, int order, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (order != 2 && order != 4 && order != 8) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Costas* d = new (std::nothrow) Costas();
-    if (!d) return QDSP_HIP_ENOMEM;
+    Costas* d = nullptr;
+    if (const int rc = op_new<Costas, costas_launch>(&d, h, order == 2 || order == 4 || order == 8, device, nchan, max_block)) return rc;
     d->order = order;
-    d->launch = launch_as<Costas, costas_launch>;
     d->par.resize((size_t)nchan * 2);
     for (int c = 0; c < nchan; c++) (void)costas_gains(1.0f, &d->par[2 * c], &d->par[2 * c + 1]);   // _loopBandwidth = 1.0f (pll.h:107)
     hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float2), sizeof(float2));
@@ -275,15 +265,10 @@ int qdsp_hip_costas_create(void** h, int device, int order, int nchan, int max_b
     if (err == hipSuccess) err = hipMalloc(&d->d_par, d->par.size() * sizeof(float));
     if (err == hipSuccess) err = hipMemcpy(d->d_par, d->par.data(), d->par.size() * sizeof(float), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        costas_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<costas_free>(h, d, err);
 }
 int qdsp_hip_costas_set_bandwidth(void* h, int chan, float bw) {
-    Costas* d = as_costas(h);
+    Costas* d = as<Costas>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     float alpha = 0.0f, beta = 0.0f;
     if (!costas_gains(bw, &alpha, &beta)) return QDSP_HIP_EINVAL;
@@ -294,14 +279,14 @@ int qdsp_hip_costas_set_bandwidth(void* h, int chan, float bw) {
     return sync_upload(d, d->d_par, d->par.data(), d->par.size() * sizeof(float));
 }
 int qdsp_hip_costas_get_gains(void* h, int chan, float* alpha, float* beta) {
-    Costas* d = as_costas(h);
+    Costas* d = as<Costas>(h);
     if (!d || !chan_ok(d, chan) || !alpha || !beta) return QDSP_HIP_EINVAL;
     *alpha = d->par[2 * chan];
     *beta = d->par[2 * chan + 1];
     return 0;
 }
 int qdsp_hip_costas_get_state(void* h, int chan, double* freq, double* phase) {
-    Costas* d = as_costas(h);
+    Costas* d = as<Costas>(h);
     if (!d || !chan_ok(d, chan) || !freq || !phase) return QDSP_HIP_EINVAL;
     double v[2];
     if (const int rc = sync_download(d, v, d->d_state[d->cur] + 2 * chan, sizeof(v))) return rc;
@@ -310,31 +295,28 @@ int qdsp_hip_costas_get_state(void* h, int chan, double* freq, double* phase) {
     return 0;
 }
 int qdsp_hip_costas_set_state(void* h, int chan, double freq, double phase) {
-    Costas* d = as_costas(h);
+    Costas* d = as<Costas>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (std::isfinite(phase) && std::fabs(phase) > (double)(2.0f * 3.1415926535f)) return QDSP_HIP_EINVAL;   // the loop keeps it inside
     return costas_fill_state(d, chan, freq, phase, false);
 }
 int qdsp_hip_costas_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Costas* d = as_costas(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Costas>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_costas_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_costas_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_costas_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Costas* d = as_costas(h);
-    return d ? costas_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Costas, costas_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_costas_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                       void* hip_stream) {
-    Costas* d = as_costas(h);
-    return d ? costas_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<Costas, costas_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_costas_reset(void* h) {
-    Costas* d = as_costas(h);
+    Costas* d = as<Costas>(h);
     return d ? costas_fill_state(d, -1, 0.0, 0.0, true) : QDSP_HIP_EINVAL;
 }
-void qdsp_hip_costas_destroy(void* h) { costas_free(as_costas(h)); }
+void qdsp_hip_costas_destroy(void* h) { costas_free(as<Costas>(h)); }
 
 }  // extern "C"

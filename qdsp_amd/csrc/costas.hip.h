@@ -51,16 +51,12 @@ struct CostasArgs {
 namespace qh {
 
 struct Costas : StreamOp {
-    Costas() : StreamOp(kCostasMagic) {}
+    static constexpr OpKind kKind = OpKind::Costas;
     int order = 2;
     double* d_state[2] = {nullptr, nullptr};
     int cur = 0;
     float* d_par = nullptr;
     std::vector<float> par;                // [nchan][2]
 };
-inline Costas* as_costas(void* h) {
-    Costas* d = static_cast<Costas*>(h);
-    return (d && d->magic == kCostasMagic) ? d : nullptr;
-}
 
 }  // namespace qh

@@ -135,13 +135,7 @@ namespace {
 int comps(const Deemp* d) { return d->kind == QDSP_HIP_DEEMP_STEREO ? 2 : 1; }
 
 void deemp_free(Deemp* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_alpha, (void*)d->d_part})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_state[0], d->d_state[1], d->d_alpha, d->d_part}); });
 }
 
 // d_in / d_out: nchan rows of `count` samples, in_stride / out_stride samples apart
@@ -210,13 +204,10 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_deemp_create(void** h, int device, int kind, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (kind != QDSP_HIP_DEEMP_MONO && kind != QDSP_HIP_DEEMP_STEREO) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Deemp* d = new (std::nothrow) Deemp();
-    if (!d) return QDSP_HIP_ENOMEM;
+    Deemp* d = nullptr;
+    const bool args_ok = kind == QDSP_HIP_DEEMP_MONO || kind == QDSP_HIP_DEEMP_STEREO;
+    if (const int rc = op_new<Deemp, deemp_launch>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
-    d->launch = launch_as<Deemp, deemp_launch>;
     d->alpha.assign(nchan, 1.0f);   // sample_rate 1, tau 0 until set: y = x
     const int nc = comps(d);
     hipError_t err = stream_op_init(d, device, nchan, max_block, nc * sizeof(float), nc * sizeof(float));
@@ -227,15 +218,10 @@ int qdsp_hip_deemp_create(void** h, int device, int kind, int nchan, int max_blo
     if (err == hipSuccess) err = hipMalloc(&d->d_alpha, (size_t)nchan * sizeof(float));
     if (err == hipSuccess) err = hipMemcpy(d->d_alpha, d->alpha.data(), (size_t)nchan * sizeof(float), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMalloc(&d->d_part, (size_t)nchan * qk::kAmMaxParts * (1 + nc) * sizeof(double));
-    if (err != hipSuccess) {
-        deemp_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<deemp_free>(h, d, err);
 }
 int qdsp_hip_deemp_set(void* h, int chan, float sample_rate, float tau) {
-    Deemp* d = as_deemp(h);
+    Deemp* d = as<Deemp>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (!std::isfinite(sample_rate) || sample_rate <= 0.0f || !std::isfinite(tau) || tau < 0.0f) return QDSP_HIP_EINVAL;
     // BFMDeemp::init / setSampleRate / setTau (filter.h:102-103), in float
@@ -246,29 +232,26 @@ int qdsp_hip_deemp_set(void* h, int chan, float sample_rate, float tau) {
     return sync_upload(d, d->d_alpha, d->alpha.data(), (size_t)d->nchan * sizeof(float));
 }
 int qdsp_hip_deemp_set_bypass(void* h, int on) {
-    Deemp* d = as_deemp(h);
+    Deemp* d = as<Deemp>(h);
     if (!d) return QDSP_HIP_EINVAL;
     d->bypass = on != 0;
     return 0;
 }
 int qdsp_hip_deemp_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Deemp* d = as_deemp(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Deemp>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_deemp_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_deemp_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_deemp_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Deemp* d = as_deemp(h);
-    return d ? deemp_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Deemp, deemp_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_deemp_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                      void* hip_stream) {
-    Deemp* d = as_deemp(h);
-    return d ? deemp_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<Deemp, deemp_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_deemp_get_state(void* h, int chan, float* l, float* r) {
-    Deemp* d = as_deemp(h);
+    Deemp* d = as<Deemp>(h);
     if (!d || !chan_ok(d, chan) || !l || (comps(d) == 2 && !r)) return QDSP_HIP_EINVAL;
     double v[2] = {0.0, 0.0};
     const int nc = comps(d);
@@ -278,7 +261,7 @@ int qdsp_hip_deemp_get_state(void* h, int chan, float* l, float* r) {
     return 0;
 }
 int qdsp_hip_deemp_set_state(void* h, int chan, float l, float r) {
-    Deemp* d = as_deemp(h);
+    Deemp* d = as<Deemp>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     const int nc = comps(d), n = chan_count(d, chan);
     std::vector<double> v((size_t)n * nc);
@@ -289,19 +272,19 @@ int qdsp_hip_deemp_set_state(void* h, int chan, float l, float r) {
     return sync_upload(d, d->d_state[d->cur] + (size_t)chan_first(chan) * nc, v.data(), v.size() * sizeof(double));
 }
 int qdsp_hip_deemp_get_alpha(void* h, int chan, float* alpha) {
-    Deemp* d = as_deemp(h);
+    Deemp* d = as<Deemp>(h);
     if (!d || !chan_ok(d, chan) || !alpha) return QDSP_HIP_EINVAL;
     *alpha = d->alpha[chan];
     return 0;
 }
 int qdsp_hip_deemp_reset(void* h) {
-    Deemp* d = as_deemp(h);
+    Deemp* d = as<Deemp>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
     for (int i = 0; i < 2; i++) HIPCHK(hipMemset(d->d_state[i], 0, (size_t)d->nchan * comps(d) * sizeof(double)));
     return 0;
 }
-void qdsp_hip_deemp_destroy(void* h) { deemp_free(as_deemp(h)); }
+void qdsp_hip_deemp_destroy(void* h) { deemp_free(as<Deemp>(h)); }
 
 }  // extern "C"

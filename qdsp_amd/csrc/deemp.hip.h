@@ -40,7 +40,7 @@ struct DeempArgs {
 namespace qh {
 
 struct Deemp : StreamOp {
-    Deemp() : StreamOp(kDeempMagic) {}
+    static constexpr OpKind kKind = OpKind::Deemp;
     int kind = 0;                          // QDSP_HIP_DEEMP_MONO / _STEREO
     bool bypass = false;
     double* d_state[2] = {nullptr, nullptr};
@@ -49,9 +49,5 @@ struct Deemp : StreamOp {
     std::vector<float> alpha;
     double* d_part = nullptr;
 };
-inline Deemp* as_deemp(void* h) {
-    Deemp* d = static_cast<Deemp*>(h);
-    return (d && d->magic == kDeempMagic) ? d : nullptr;
-}
 
 }  // namespace qh

@@ -309,12 +309,7 @@ int thr_launch(Threshold* d, const void* d_in, int64_t count, int64_t in_stride,
 }
 
 void thr_free(Threshold* d) {
-    if (!d) return;
-    stream_op_unregister(d);
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    stream_op_release(d);
-    delete d;
+    op_free(d, [] {});
 }
 
 // ---- Deframer ----
@@ -326,16 +321,11 @@ int64_t df_out_count(const StreamOp* op, int64_t count) {
 }
 
 void df_free(Deframer* d) {
-    if (!d) return;
-    stream_op_unregister(d);
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_sync, (void*)d->d_tail[0], (void*)d->d_tail[1], (void*)d->d_carry[0], (void*)d->d_carry[1], (void*)d->d_state[0],
-                    (void*)d->d_state[1], (void*)d->d_words, (void*)d->d_starts, (void*)d->d_meta, (void*)d->d_counts})
-        if (p) (void)hipFree(p);
-    if (d->h_count) (void)hipHostFree(d->h_count);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] {
+        hip_free_all({d->d_sync, d->d_tail[0], d->d_tail[1], d->d_carry[0], d->d_carry[1], d->d_state[0], d->d_state[1], d->d_words, d->d_starts,
+                      d->d_meta, d->d_counts});
+        if (d->h_count) (void)hipHostFree(d->h_count);
+    });
 }
 
 // the match words and frame starts of calls of up to `count` bytes per row (a larger call than any before synchronises the device)
@@ -441,51 +431,36 @@ using namespace qh;
 extern "C" {
 
 int qdsp_hip_threshold_create(void** h, int device, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Threshold* d = new (std::nothrow) Threshold();
-    if (!d) return QDSP_HIP_ENOMEM;
-    d->launch = launch_as<Threshold, thr_launch>;
-    if (const hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float), 1)) {
-        delete d;
-        return -(int)err;
-    }
-    stream_op_register(d, kKindThreshold);
-    *h = d;
-    return 0;
+    Threshold* d = nullptr;
+    if (const int rc = op_new<Threshold, thr_launch>(&d, h, true, device, nchan, max_block)) return rc;
+    return op_created<thr_free>(h, d, stream_op_init(d, device, nchan, max_block, sizeof(float), 1));
 }
 int qdsp_hip_threshold_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, const int* d_in_counts, void* d_out,
                                          int64_t out_stride, void* hip_stream) {
-    Threshold* d = as_threshold(h);
+    Threshold* d = as<Threshold>(h);
     return d ? thr_launch_counts(d, d_in, count, in_stride, d_in_counts, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_threshold_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Threshold* d = as_threshold(h);
-    return d ? thr_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Threshold, thr_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_threshold_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Threshold* d = as_threshold(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Threshold>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_threshold_process(void* h, const float* in, int count, uint8_t* out) {
     return qdsp_hip_threshold_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
-void qdsp_hip_threshold_destroy(void* h) { thr_free(as_threshold(h)); }
+void qdsp_hip_threshold_destroy(void* h) { thr_free(as<Threshold>(h)); }
 int qdsp_hip_threshold_span(void) { return qk::kThrNT * qk::kThrPer; }
 
 int qdsp_hip_deframer_create(void** h, int device, int kind, int nchan, int max_block, int frame_len, const uint8_t* sync, int sync_len) {
-    if (h) *h = nullptr;
-    if ((kind != 0 && kind != 1) || frame_len < 1 || frame_len > (1 << 20) || !sync || sync_len < 1 || sync_len > qk::kDfMaxSync) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Deframer* d = new (std::nothrow) Deframer();
-    if (!d) return QDSP_HIP_ENOMEM;
+    Deframer* d = nullptr;
+    const bool args_ok = (kind == 0 || kind == 1) && frame_len >= 1 && frame_len <= (1 << 20) && sync && sync_len >= 1 && sync_len <= qk::kDfMaxSync;
+    if (const int rc = op_new<Deframer, df_launch, df_out_count>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
     d->frame_len = frame_len;
     d->frame_bytes = (frame_len + 7) / 8;
     d->sync_len = sync_len;
     d->sync.assign(sync, sync + sync_len);
-    d->launch = launch_as<Deframer, df_launch>;
-    d->out_count = df_out_count;
     hipError_t err = stream_op_init(d, device, nchan, max_block, kind ? sizeof(float) : 1, 1);
     d->nchan = nchan;
     if (err == hipSuccess && max_block > 0) {
@@ -511,23 +486,17 @@ int qdsp_hip_deframer_create(void** h, int device, int kind, int nchan, int max_
         if (rc) err = (hipError_t)(-rc);
     }
     if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        df_free(d);
-        return -(int)err;
-    }
-    stream_op_register(d, kKindDeframer);
-    *h = d;
-    return 0;
+    return op_created<df_free>(h, d, err);
 }
 int qdsp_hip_deframer_set_sync(void* h, const uint8_t* sync, int sync_len) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     if (!d || !sync || sync_len != d->sync_len) return QDSP_HIP_EINVAL;
     if (const int rc = sync_upload(d, d->d_sync, sync, (size_t)sync_len)) return rc;
     d->sync.assign(sync, sync + sync_len);
     return 0;
 }
 int qdsp_hip_deframer_get_state(void* h, int chan, int* bits_read, int* bad, int* after) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     if (!d || !chan_ok(d, chan) || !bits_read || !bad || !after) return QDSP_HIP_EINVAL;
     int v[3];
     if (const int rc = sync_download(d, v, d->d_state[d->cur] + (size_t)chan * qk::kDfState, sizeof(v))) return rc;
@@ -537,7 +506,7 @@ int qdsp_hip_deframer_get_state(void* h, int chan, int* bits_read, int* bad, int
     return 0;
 }
 int qdsp_hip_deframer_set_state(void* h, int chan, int bits_read, int bad, int after) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (bits_read < -1 || bits_read >= d->frame_len || bad < 0 || bad > 5 || (after != 0 && after != 1)) return QDSP_HIP_EINVAL;
     if (bits_read >= 0 && after) return QDSP_HIP_EINVAL;      // `after` is only ever set between two frames
@@ -549,16 +518,16 @@ int qdsp_hip_deframer_set_state(void* h, int chan, int bits_read, int bad, int a
     return 0;
 }
 int64_t qdsp_hip_deframer_out_size(void* h, int64_t count) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     return (d && count >= 0) ? df_out_size(d, count) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deframer_frame_bytes(void* h) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     return d ? d->frame_bytes : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deframer_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, const int* d_in_counts, void* d_out,
                                         int64_t out_stride_bytes, int* d_counts, void* hip_stream) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     if (!d) return QDSP_HIP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (const int rc = df_launch_counts(d, d_in, count, in_stride, d_in_counts, d_out, out_stride_bytes, s)) return rc;
@@ -566,16 +535,16 @@ int qdsp_hip_deframer_process_batch_dev(void* h, const void* d_in, int64_t count
     return 0;
 }
 int qdsp_hip_deframer_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     return d ? df_launch(d, d_in, count, count, d_out, df_out_count(d, count), static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deframer_get_counts(void* h, int* counts) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     if (!d || !counts) return QDSP_HIP_EINVAL;
     return sync_download(d, counts, d->d_counts, (size_t)d->nchan * sizeof(int));
 }
 int qdsp_hip_deframer_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     // the frame count is returned, so the call has to have run: an output link that hands over without waiting cannot be served
     if (!d || (out_link != QDSP_HIP_LINK_HOST && out_link != QDSP_HIP_LINK_DEVICE)) return QDSP_HIP_EINVAL;
     const int64_t rc = stream_op_process_ex(d, in, in_link, count, out, out_link);
@@ -586,13 +555,13 @@ int qdsp_hip_deframer_process(void* h, const void* in, int count, uint8_t* out) 
     return qdsp_hip_deframer_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_deframer_reset(void* h) {
-    Deframer* d = as_deframer(h);
+    Deframer* d = as<Deframer>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
     return df_fill_initial(d);
 }
-void qdsp_hip_deframer_destroy(void* h) { df_free(as_deframer(h)); }
+void qdsp_hip_deframer_destroy(void* h) { df_free(as<Deframer>(h)); }
 int qdsp_hip_deframer_tile(void) { return qk::kDfTile; }
 int qdsp_hip_deframer_pack_span(void) { return qk::kDfNT * 8; }
 

@@ -70,14 +70,11 @@ struct DeframeArgs {
 namespace qh {
 
 struct Threshold : StreamOp {
-    Threshold() : StreamOp(0) {}        // known by its address (stream_op.h: kinds without a magic)
+    static constexpr OpKind kKind = OpKind::Threshold;
 };
-inline Threshold* as_threshold(void* h) {
-    return static_cast<Threshold*>(stream_op_registered(h, kKindThreshold));
-}
 
 struct Deframer : StreamOp {
-    Deframer() : StreamOp(0) {}
+    static constexpr OpKind kKind = OpKind::Deframer;
     int kind = 0;                          // 0 uint8_t rows, 1 float rows thresholded on load
     int frame_len = 0, frame_bytes = 0, sync_len = 0;
     std::vector<unsigned char> sync;
@@ -93,8 +90,5 @@ struct Deframer : StreamOp {
     int* d_counts = nullptr;
     int* h_count = nullptr;                // pinned: row 0's frame count of the last process_ex call
 };
-inline Deframer* as_deframer(void* h) {
-    return static_cast<Deframer*>(stream_op_registered(h, kKindDeframer));
-}
 
 }  // namespace qh

@@ -194,32 +194,25 @@ namespace {
 int out_floats(const Demod* d) { return d->kind == QDSP_HIP_DEMOD_FM_STEREO ? 2 : 1; }
 bool is_fm(const Demod* d) { return d->kind == QDSP_HIP_DEMOD_FM || d->kind == QDSP_HIP_DEMOD_FM_STEREO; }
 
-Demod* as_kind(void* h, bool ssb) {
-    Demod* d = as_demod(h);
-    return (d && (d->kind == kDemodSsb) == ssb) ? d : nullptr;
+template <bool SSB> Demod* as_kind(void* h) {
+    Demod* d = as<Demod>(h);
+    return (d && (d->kind == kDemodSsb) == SSB) ? d : nullptr;
 }
+constexpr auto as_plain = as_kind<false>, as_ssb = as_kind<true>;
 
 void demod_free(Demod* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_phase[0], (void*)d->d_phase[1], (void*)d->d_speed, (void*)d->d_part})
-        if (p) (void)hipFree(p);
-    if (d->nco) destroy(d->nco);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] {
+        hip_free_all({d->d_phase[0], d->d_phase[1], d->d_speed, d->d_part});
+        if (d->nco) destroy(d->nco);
+    });
 }
 
 int demod_launch(Demod* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
 
 int demod_new(void** h, int device, int kind, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (kind < 0 || kind > kDemodSsb) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Demod* d = new (std::nothrow) Demod();
-    if (!d) return QDSP_HIP_ENOMEM;
+    Demod* d = nullptr;
+    if (const int rc = op_new<Demod, demod_launch>(&d, h, kind >= 0 && kind <= kDemodSsb, device, nchan, max_block)) return rc;
     d->kind = kind;
-    d->launch = launch_as<Demod, demod_launch>;
     // phasorSpeed of sampleRate == deviation until set_fm: out = phase step / (2 pi)
     d->rate.assign(nchan, 1.0f);
     d->dev.assign(nchan, 1.0f);
@@ -234,12 +227,7 @@ int demod_new(void** h, int device, int kind, int nchan, int max_block) {
         if (err == hipSuccess) err = hipMemcpy(d->d_speed, d->speed.data(), (size_t)nchan * sizeof(float), hipMemcpyHostToDevice);
     }
     if (err == hipSuccess && kind == QDSP_HIP_DEMOD_AM) err = hipMalloc(&d->d_part, (size_t)nchan * qk::kAmMaxParts * sizeof(double));
-    if (err != hipSuccess) {
-        demod_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<demod_free>(h, d, err);
 }
 
 // d_in: nchan rows of `count` complex samples, in_stride apart; d_out: nchan rows of `count` outputs, out_stride apart
@@ -334,7 +322,7 @@ int qdsp_hip_demod_create(void** h, int device, int kind, int nchan, int max_blo
     return demod_new(h, device, kind, nchan, max_block);
 }
 int qdsp_hip_demod_set_fm(void* h, int chan, float sample_rate, float deviation) {
-    Demod* d = as_kind(h, false);
+    Demod* d = as_plain(h);
     if (!d || !is_fm(d) || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     // FloatFMDemod::init / setSampleRate / setDeviation (demodulator.h:42,62,72), in float
     const float speed = (2 * 3.1415926535f) / (sample_rate / deviation);
@@ -347,34 +335,31 @@ int qdsp_hip_demod_set_fm(void* h, int chan, float sample_rate, float deviation)
     return sync_upload(d, d->d_speed, d->speed.data(), (size_t)d->nchan * sizeof(float));
 }
 int qdsp_hip_demod_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Demod* d = as_kind(h, false);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Demod, as_plain>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_demod_process(void* h, const float* in_iq, int count, void* out) {
     return qdsp_hip_demod_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_demod_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Demod* d = as_kind(h, false);
-    return d ? demod_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Demod, demod_launch, as_plain>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_demod_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                      void* hip_stream) {
-    Demod* d = as_kind(h, false);
-    return d ? demod_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<Demod, demod_launch, as_plain>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_demod_get_phase(void* h, int chan, float* phase) {
-    Demod* d = as_kind(h, false);
+    Demod* d = as_plain(h);
     if (!d || !is_fm(d) || !chan_ok(d, chan) || !phase) return QDSP_HIP_EINVAL;
     return sync_download(d, phase, d->d_phase[d->cur] + chan, sizeof(float));
 }
 int qdsp_hip_demod_set_phase(void* h, int chan, float phase) {
-    Demod* d = as_kind(h, false);
+    Demod* d = as_plain(h);
     if (!d || !is_fm(d) || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     const std::vector<float> v((size_t)chan_count(d, chan), phase);
     return sync_upload(d, d->d_phase[d->cur] + chan_first(chan), v.data(), v.size() * sizeof(float));
 }
 int qdsp_hip_demod_reset(void* h) {
-    Demod* d = as_kind(h, false);
+    Demod* d = as_plain(h);
     if (!d) return QDSP_HIP_EINVAL;
     if (!is_fm(d)) return 0;   // (AM keeps no state between calls)
     HIPCHK(hipSetDevice(d->device));
@@ -382,7 +367,7 @@ int qdsp_hip_demod_reset(void* h) {
     for (int i = 0; i < 2; i++) HIPCHK(hipMemset(d->d_phase[i], 0, (size_t)d->nchan * sizeof(float)));
     return 0;
 }
-void qdsp_hip_demod_destroy(void* h) { demod_free(as_kind(h, false)); }
+void qdsp_hip_demod_destroy(void* h) { demod_free(as_plain(h)); }
 
 // ---- SSBDemod: the xlate_cf32 NCO, real part out --------------------------------------------------
 int qdsp_hip_ssb_cf32_create(void** h, int device, float phase_inc_re, float phase_inc_im, int max_block) {
@@ -402,43 +387,41 @@ int qdsp_hip_ssb_cf32_create(void** h, int device, float phase_inc_re, float pha
     return 0;
 }
 int qdsp_hip_ssb_cf32_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Demod* d = as_kind(h, true);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Demod, as_ssb>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_ssb_cf32_process(void* h, const float* in_iq, int count, float* out) {
     return qdsp_hip_ssb_cf32_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_ssb_cf32_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Demod* d = as_kind(h, true);
-    return d ? demod_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Demod, demod_launch, as_ssb>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_ssb_cf32_set_phase_inc(void* h, float re, float im) {
-    Demod* d = as_kind(h, true);
+    Demod* d = as_ssb(h);
     if (!d || (re == 0.0f && im == 0.0f)) return QDSP_HIP_EINVAL;
     set_inc(d->nco, re, im);
     return 0;
 }
 int qdsp_hip_ssb_cf32_get_phase(void* h, float* re, float* im) {
-    Demod* d = as_kind(h, true);
+    Demod* d = as_ssb(h);
     return d ? get_phase(d->nco, re, im) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ssb_cf32_set_phase(void* h, float re, float im) {
-    Demod* d = as_kind(h, true);
+    Demod* d = as_ssb(h);
     return d ? set_phase(d->nco, re, im) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ssb_cf32_advance(void* h, int64_t n) {
-    Demod* d = as_kind(h, true);
+    Demod* d = as_ssb(h);
     if (!d) return QDSP_HIP_EINVAL;
     apply_pending_inc(d->nco);
     d->nco->phase += (unsigned long long)n * d->nco->dphase;
     return 0;
 }
 int qdsp_hip_ssb_cf32_set_volk_gain(void* h, int on) {
-    Demod* d = as_kind(h, true);
+    Demod* d = as_ssb(h);
     if (!d) return QDSP_HIP_EINVAL;
     d->nco->volk_gain = on != 0;
     return 0;
 }
-void qdsp_hip_ssb_cf32_destroy(void* h) { demod_free(as_kind(h, true)); }
+void qdsp_hip_ssb_cf32_destroy(void* h) { demod_free(as_ssb(h)); }
 
 }  // extern "C"

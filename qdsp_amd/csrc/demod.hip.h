@@ -97,7 +97,7 @@ namespace qh {
 // StreamOp it begins with (stream_op.h)
 constexpr int kDemodSsb = 3;                   // (QDSP_HIP_DEMOD_FM / _FM_STEREO / _AM are 0..2)
 struct Demod : StreamOp {
-    Demod() : StreamOp(kDemodMagic) {}
+    static constexpr OpKind kKind = OpKind::Demod;
     int kind = 0;
     // FM: carried phase, double-buffered (lanes of one launch read slot cur, the last sample's lane writes cur ^ 1)
     float* d_phase[2] = {nullptr, nullptr};
@@ -109,10 +109,6 @@ struct Demod : StreamOp {
     // SSB: the NCO state of an xlate_cf32 engine (never launched through the engine itself)
     Engine* nco = nullptr;
 };
-inline Demod* as_demod(void* h) {
-    Demod* d = static_cast<Demod*>(h);
-    return (d && d->magic == kDemodMagic) ? d : nullptr;
-}
 void launch_fm_mono(const qk::FmArgs& a, int tiles, int nchan, hipStream_t s);
 
 }  // namespace qh

@@ -173,39 +173,23 @@ int64_t out_count(const StreamOp* op, int64_t count) {   // (StreamOp::out_count
 }
 
 void ffagc_free(FfAgc* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_hist[0], (void*)d->d_hist[1]})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_hist[0], d->d_hist[1]}); });
 }
 
 int64_t ffagc_launch(FfAgc* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
 
 int ffagc_new(void** h, int device, int kind, int nchan, int max_block, int window) {
-    if (h) *h = nullptr;
-    if (kind != QDSP_HIP_FFAGC_REAL && kind != QDSP_HIP_FFAGC_COMPLEX) return QDSP_HIP_EINVAL;
-    if (window < 1 || window > qk::kFfAgcMaxWindow) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    FfAgc* d = new (std::nothrow) FfAgc();
-    if (!d) return QDSP_HIP_ENOMEM;
+    FfAgc* d = nullptr;
+    const bool args_ok = (kind == QDSP_HIP_FFAGC_REAL || kind == QDSP_HIP_FFAGC_COMPLEX) && window >= 1 && window <= qk::kFfAgcMaxWindow;
+    if (const int rc = op_new<FfAgc, ffagc_launch, out_count>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
     d->window = window;
-    d->launch = launch_as<FfAgc, ffagc_launch>;
-    d->out_count = out_count;
     hipError_t err = stream_op_init(d, device, nchan, max_block, comps(d) * sizeof(float), comps(d) * sizeof(float));
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
         err = hipMalloc(&d->d_hist[i], hist_bytes(d));
         if (err == hipSuccess) err = hipMemset(d->d_hist[i], 0, hist_bytes(d));
     }
-    if (err != hipSuccess) {
-        ffagc_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<ffagc_free>(h, d, err);
 }
 
 // d_in: nchan rows of `count` samples, in_stride apart; d_out: nchan rows of the call's outputs, out_stride apart.  Returns the
@@ -273,36 +257,35 @@ int qdsp_hip_ffagc_create(void** h, int device, int kind, int nchan, int max_blo
     return ffagc_new(h, device, kind, nchan, max_block, window);
 }
 int qdsp_hip_ffagc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    FfAgc* d = as_ff_agc(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<FfAgc>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_ffagc_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_ffagc_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int64_t qdsp_hip_ffagc_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     if (!d) return QDSP_HIP_EINVAL;
     return ffagc_launch(d, d_in, count, count, d_out, out_count(d, count), static_cast<hipStream_t>(hip_stream));
 }
 int64_t qdsp_hip_ffagc_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                          void* hip_stream) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     return d ? ffagc_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
 }
 int64_t qdsp_hip_ffagc_out_size(void* h, int64_t count) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     return (d && count >= 0) ? out_count(d, count) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ffagc_window(void* h) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     return d ? d->window : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ffagc_fill(void* h) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     return d ? d->fill : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_ffagc_get_history(void* h, int chan, float* hist) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     if (!d || chan < 0 || chan >= d->nchan || !hist) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
@@ -312,7 +295,7 @@ int qdsp_hip_ffagc_get_history(void* h, int chan, float* hist) {
     return 0;
 }
 int qdsp_hip_ffagc_set_history(void* h, int chan, const float* hist, int fill) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     if (!d || chan < -1 || chan >= d->nchan || fill < 0 || fill > d->window - 1 || (fill > 0 && !hist)) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
@@ -324,7 +307,7 @@ int qdsp_hip_ffagc_set_history(void* h, int chan, const float* hist, int fill) {
     return 0;
 }
 int qdsp_hip_ffagc_reset(void* h) {
-    FfAgc* d = as_ff_agc(h);
+    FfAgc* d = as<FfAgc>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
@@ -332,6 +315,6 @@ int qdsp_hip_ffagc_reset(void* h) {
     d->fill = 0;
     return 0;
 }
-void qdsp_hip_ffagc_destroy(void* h) { ffagc_free(as_ff_agc(h)); }
+void qdsp_hip_ffagc_destroy(void* h) { ffagc_free(as<FfAgc>(h)); }
 
 }  // extern "C"

@@ -63,16 +63,12 @@ constexpr int ff_agc_lds(int W) { return 2 * ff_agc_L(W) * (int)sizeof(float); }
 namespace qh {
 
 struct FfAgc : StreamOp {
-    FfAgc() : StreamOp(kFfAgcMagic) {}
+    static constexpr OpKind kKind = OpKind::FfAgc;
     int kind = 0;                          // qk::kFfAgcReal / kFfAgcComplex
     int window = 1024;
     float* d_hist[2] = {nullptr, nullptr}; // read from slot cur, written to cur ^ 1
     int cur = 0;
     int fill = 0;                          // samples held, the same for every row
 };
-inline FfAgc* as_ff_agc(void* h) {
-    FfAgc* d = static_cast<FfAgc*>(h);
-    return (d && d->magic == kFfAgcMagic) ? d : nullptr;
-}
 
 }  // namespace qh

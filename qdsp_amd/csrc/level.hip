@@ -146,30 +146,22 @@ namespace qh {
 
 namespace {
 int comps(const Level* d) { return d->kind == qk::kLevelSquelch ? 2 : 1; }
-Level* as_kind(void* h, int kind) {
-    Level* d = as_level(h);
-    return (d && d->kind == kind) ? d : nullptr;
+template <int KIND> Level* as_kind(void* h) {
+    Level* d = as<Level>(h);
+    return (d && d->kind == KIND) ? d : nullptr;
 }
+constexpr auto as_squelch = as_kind<qk::kLevelSquelch>, as_agc = as_kind<qk::kLevelAgc>;
 
 void level_free(Level* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {d->d_state[0], d->d_state[1], (void*)d->d_param, (void*)d->d_part})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_state[0], d->d_state[1], d->d_param, d->d_part}); });
 }
 
 int level_launch(Level* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
 
 int level_new(void** h, int device, int kind, int nchan, int max_block, float param0) {
-    if (h) *h = nullptr;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Level* d = new (std::nothrow) Level();
-    if (!d) return QDSP_HIP_ENOMEM;
+    Level* d = nullptr;
+    if (const int rc = op_new<Level, level_launch>(&d, h, true, device, nchan, max_block)) return rc;
     d->kind = kind;
-    d->launch = launch_as<Level, level_launch>;
     d->param.assign(nchan, param0);
     d->fall.assign(nchan, 0.0f);
     d->rate.assign(nchan, 1.0f);
@@ -181,12 +173,7 @@ int level_new(void** h, int device, int kind, int nchan, int max_block, float pa
     if (err == hipSuccess) err = hipMalloc(&d->d_param, (size_t)nchan * sizeof(float));
     if (err == hipSuccess) err = hipMemcpy(d->d_param, d->param.data(), (size_t)nchan * sizeof(float), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMalloc(&d->d_part, (size_t)nchan * qk::kAmMaxParts * sizeof(double));
-    if (err != hipSuccess) {
-        level_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<level_free>(h, d, err);
 }
 
 int push_param(Level* d, int chan, float v) {
@@ -270,43 +257,40 @@ int qdsp_hip_squelch_create(void** h, int device, int nchan, int max_block) {
     return level_new(h, device, qk::kLevelSquelch, nchan, max_block, -50.0f);   // _level (processing.h:486)
 }
 int qdsp_hip_squelch_set_level(void* h, int chan, float level) {
-    Level* d = as_kind(h, qk::kLevelSquelch);
+    Level* d = as_squelch(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     return push_param(d, chan, level);
 }
 int qdsp_hip_squelch_get_open(void* h, int chan, int* open) {
-    Level* d = as_kind(h, qk::kLevelSquelch);
+    Level* d = as_squelch(h);
     if (!d || !chan_ok(d, chan) || !open) return QDSP_HIP_EINVAL;
     return get_state(d, chan, open);
 }
 int qdsp_hip_squelch_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Level* d = as_kind(h, qk::kLevelSquelch);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Level, as_squelch>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_squelch_process(void* h, const float* in_iq, int count, float* out_iq) {
     return qdsp_hip_squelch_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out_iq, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_squelch_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Level* d = as_kind(h, qk::kLevelSquelch);
-    return d ? level_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Level, level_launch, as_squelch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_squelch_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                        void* hip_stream) {
-    Level* d = as_kind(h, qk::kLevelSquelch);
-    return d ? level_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<Level, level_launch, as_squelch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_squelch_reset(void* h) {
-    Level* d = as_kind(h, qk::kLevelSquelch);
+    Level* d = as_squelch(h);
     return d ? level_reset(d) : QDSP_HIP_EINVAL;
 }
-void qdsp_hip_squelch_destroy(void* h) { level_free(as_kind(h, qk::kLevelSquelch)); }
+void qdsp_hip_squelch_destroy(void* h) { level_free(as_squelch(h)); }
 
 // ---- AGC ----------------------------------------------------------------------------------------
 int qdsp_hip_agc_create(void** h, int device, int nchan, int max_block) {
     return level_new(h, device, qk::kLevelAgc, nchan, max_block, 0.0f);   // fall_rate 0 / sample_rate 1
 }
 int qdsp_hip_agc_set(void* h, int chan, float fall_rate, float sample_rate) {
-    Level* d = as_kind(h, qk::kLevelAgc);
+    Level* d = as_agc(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (!std::isfinite(sample_rate) || sample_rate <= 0.0f || !std::isfinite(fall_rate)) return QDSP_HIP_EINVAL;
     for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) {
@@ -316,36 +300,33 @@ int qdsp_hip_agc_set(void* h, int chan, float fall_rate, float sample_rate) {
     return push_param(d, chan, fall_rate / sample_rate);   // _CorrectedFallRate (processing.h:93), in float
 }
 int qdsp_hip_agc_get_level(void* h, int chan, float* level) {
-    Level* d = as_kind(h, qk::kLevelAgc);
+    Level* d = as_agc(h);
     if (!d || !chan_ok(d, chan) || !level) return QDSP_HIP_EINVAL;
     return get_state(d, chan, level);
 }
 int qdsp_hip_agc_set_level(void* h, int chan, float level) {
-    Level* d = as_kind(h, qk::kLevelAgc);
+    Level* d = as_agc(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     const std::vector<float> v((size_t)chan_count(d, chan), level);
     return sync_upload(d, static_cast<float*>(d->d_state[d->cur]) + chan_first(chan), v.data(), v.size() * sizeof(float));
 }
 int qdsp_hip_agc_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Level* d = as_kind(h, qk::kLevelAgc);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<Level, as_agc>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_agc_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_agc_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_agc_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Level* d = as_kind(h, qk::kLevelAgc);
-    return d ? level_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<Level, level_launch, as_agc>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_agc_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                    void* hip_stream) {
-    Level* d = as_kind(h, qk::kLevelAgc);
-    return d ? level_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<Level, level_launch, as_agc>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_agc_reset(void* h) {
-    Level* d = as_kind(h, qk::kLevelAgc);
+    Level* d = as_agc(h);
     return d ? level_reset(d) : QDSP_HIP_EINVAL;
 }
-void qdsp_hip_agc_destroy(void* h) { level_free(as_kind(h, qk::kLevelAgc)); }
+void qdsp_hip_agc_destroy(void* h) { level_free(as_agc(h)); }
 
 }  // extern "C"

@@ -64,7 +64,7 @@ __device__ __forceinline__ float agc_level(float level, float cfr, long long cou
 namespace qh {
 
 struct Level : StreamOp {
-    Level() : StreamOp(kLevelMagic) {}
+    static constexpr OpKind kKind = OpKind::Level;
     int kind = 0;                          // qk::kLevelSquelch / kLevelAgc
     void* d_state[2] = {nullptr, nullptr}; // 4 bytes per channel
     int cur = 0;
@@ -73,9 +73,5 @@ struct Level : StreamOp {
     std::vector<float> fall, rate;         // AGC
     double* d_part = nullptr;
 };
-inline Level* as_level(void* h) {
-    Level* d = static_cast<Level*>(h);
-    return (d && d->magic == kLevelMagic) ? d : nullptr;
-}
 
 }  // namespace qh

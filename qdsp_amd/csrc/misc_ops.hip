@@ -16,7 +16,7 @@ struct Math {
 };
 Math* as_math(void* h) {
     Math* m = static_cast<Math*>(h);
-    return (m && m->magic == kMathMagic) ? m : nullptr;
+    return (m && !as_stream_op(h) && m->magic == kMathMagic) ? m : nullptr;   // (the table first: a StreamOp is not read as a Math)
 }
 int math_ensure(Math* m, int count) {
     if (count <= m->max_block) return 0;
@@ -176,8 +176,8 @@ int qdsp_hip_set_done_event(void* h, void* ev) {
 
 int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* block, int* lds) {
     const Launch* l = nullptr;
-    if (Chan* c = as_chan(h)) l = &c->last;
-    else if (StreamOp* d = as_stream_op(h)) l = &d->last;
+    if (StreamOp* d = as_stream_op(h)) l = &d->last;   // (the table first: a StreamOp is not read as something else)
+    else if (Chan* c = as_chan(h)) l = &c->last;
     else if (Engine* e = any_engine(h)) l = &e->last;
     if (!l) return QDSP_HIP_EINVAL;
     if (name && name_len > 0) { strncpy(name, l->name, name_len - 1); name[name_len - 1] = 0; }

@@ -289,14 +289,10 @@ bool mmcr_limits(float omega, float g_omega, float g_mu, float rel, float* o_min
 }
 
 void mmcr_free(Mmcr* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_state[0], (void*)d->d_state[1], (void*)d->d_par, (void*)d->d_taps, (void*)d->d_counts})
-        if (p) (void)hipFree(p);
-    if (d->h_count) (void)hipHostFree(d->h_count);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] {
+        hip_free_all({d->d_state[0], d->d_state[1], d->d_par, d->d_taps, d->d_counts});
+        if (d->h_count) (void)hipHostFree(d->h_count);
+    });
 }
 
 void mmcr_min_step(Mmcr* d) {
@@ -401,15 +397,11 @@ extern "C" {
 
 int qdsp_hip_mmcr_create(void** h, int device, int kind, int nchan, int max_block, float omega, float gain_omega, float mu_gain,
                          float rel_limit) {
-    if (h) *h = nullptr;
     float o_min = 0.0f, o_max = 0.0f, lo = 0.0f;
-    if ((kind != 0 && kind != 1) || !mmcr_limits(omega, gain_omega, mu_gain, rel_limit, &o_min, &o_max, &lo)) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Mmcr* d = new (std::nothrow) Mmcr();
-    if (!d) return QDSP_HIP_ENOMEM;
+    const bool args_ok = (kind == 0 || kind == 1) && mmcr_limits(omega, gain_omega, mu_gain, rel_limit, &o_min, &o_max, &lo);
+    Mmcr* d = nullptr;
+    if (const int rc = op_new<Mmcr, mmcr_launch, mmcr_out_count>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
-    d->launch = launch_as<Mmcr, mmcr_launch>;
-    d->out_count = mmcr_out_count;
     d->omega.assign((size_t)nchan, omega);
     d->rel.assign((size_t)nchan, rel_limit);
     d->par.resize((size_t)nchan * qk::kMmcrPar);
@@ -440,27 +432,22 @@ int qdsp_hip_mmcr_create(void** h, int device, int kind, int nchan, int max_bloc
         if (rc) err = (hipError_t)(-rc);
     }
     if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        mmcr_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<mmcr_free>(h, d, err);
 }
 int qdsp_hip_mmcr_set_omega(void* h, int chan, float omega) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     return d ? mmcr_set(d, chan, 0, omega, 0.0f) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_set_gains(void* h, int chan, float gain_omega, float mu_gain) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     return d ? mmcr_set(d, chan, 1, gain_omega, mu_gain) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_set_limit(void* h, int chan, float rel_limit) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     return d ? mmcr_set(d, chan, 2, rel_limit, 0.0f) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_get_state(void* h, int chan, float* mu, float* dyn_omega, int* next) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d || !chan_ok(d, chan) || !mu || !dyn_omega || !next) return QDSP_HIP_EINVAL;
     float v[3];
     if (const int rc = sync_download(d, v, d->d_state[d->cur] + (size_t)chan * qk::kMmcrState, sizeof(v))) return rc;
@@ -470,7 +457,7 @@ int qdsp_hip_mmcr_get_state(void* h, int chan, float* mu, float* dyn_omega, int*
     return 0;
 }
 int qdsp_hip_mmcr_set_state(void* h, int chan, float mu, float dyn_omega, int next) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     if (!(mu >= 0.0f && mu < 1.0f) || !std::isfinite(dyn_omega) || next < 0 || next > (1 << 21)) return QDSP_HIP_EINVAL;
     float v[3] = {mu, dyn_omega, 0.0f};
@@ -482,17 +469,17 @@ int qdsp_hip_mmcr_set_state(void* h, int chan, float mu, float dyn_omega, int ne
     return 0;
 }
 int64_t qdsp_hip_mmcr_out_size(void* h, int64_t count) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     return (d && count >= 0) ? mmcr_out_size(d, count) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_get_interp_taps(void* h, float* taps) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d || !taps) return QDSP_HIP_EINVAL;
     memcpy(taps, d->taps.data(), qk::kMmcrTable * sizeof(float));
     return 0;
 }
 int qdsp_hip_mmcr_set_interp_taps(void* h, const float* taps) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d || !taps) return QDSP_HIP_EINVAL;
     for (int i = 0; i < qk::kMmcrTable; i++)
         if (!std::isfinite(taps[i])) return QDSP_HIP_EINVAL;
@@ -502,7 +489,7 @@ int qdsp_hip_mmcr_set_interp_taps(void* h, const float* taps) {
 }
 int qdsp_hip_mmcr_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                     int* d_counts, void* hip_stream) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d) return QDSP_HIP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (const int rc = mmcr_launch(d, d_in, count, in_stride, d_out, out_stride, s)) return rc;
@@ -510,16 +497,16 @@ int qdsp_hip_mmcr_process_batch_dev(void* h, const void* d_in, int64_t count, in
     return 0;
 }
 int qdsp_hip_mmcr_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     return d ? mmcr_launch(d, d_in, count, count, d_out, mmcr_out_size(d, count), static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_get_counts(void* h, int* counts) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d || !counts) return QDSP_HIP_EINVAL;
     return sync_download(d, counts, d->d_counts, (size_t)d->nchan * sizeof(int));
 }
 int qdsp_hip_mmcr_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     // the count is returned, so the call has to have run: an output link that hands over without waiting cannot be served
     if (!d || (out_link != QDSP_HIP_LINK_HOST && out_link != QDSP_HIP_LINK_DEVICE)) return QDSP_HIP_EINVAL;
     const int64_t rc = stream_op_process_ex(d, in, in_link, count, out, out_link);
@@ -530,13 +517,13 @@ int qdsp_hip_mmcr_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_mmcr_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_mmcr_reset(void* h) {
-    Mmcr* d = as_mmcr(h);
+    Mmcr* d = as<Mmcr>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemset(d->d_counts, 0, (size_t)d->nchan * sizeof(int)));
     return mmcr_fill_initial(d, 0, d->nchan, true);
 }
-void qdsp_hip_mmcr_destroy(void* h) { mmcr_free(as_mmcr(h)); }
+void qdsp_hip_mmcr_destroy(void* h) { mmcr_free(as<Mmcr>(h)); }
 
 }  // extern "C"

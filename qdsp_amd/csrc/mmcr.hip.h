@@ -59,7 +59,7 @@ struct MmcrArgs {
 namespace qh {
 
 struct Mmcr : StreamOp {
-    Mmcr() : StreamOp(kMmcrMagic) {}
+    static constexpr OpKind kKind = OpKind::Mmcr;
     int kind = 0;                          // 0 float rows, 1 complex_t rows
     float* d_state[2] = {nullptr, nullptr};
     int cur = 0;
@@ -72,9 +72,5 @@ struct Mmcr : StreamOp {
     std::vector<float> taps;               // [129][8]
     int64_t min_step = 1;                  // floor(min over rows of omegaMin - |muGain|)
 };
-inline Mmcr* as_mmcr(void* h) {
-    Mmcr* d = static_cast<Mmcr*>(h);
-    return (d && d->magic == kMmcrMagic) ? d : nullptr;
-}
 
 }  // namespace qh

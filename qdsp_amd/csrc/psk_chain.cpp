@@ -10,8 +10,6 @@
 // process_ex reads once the shared host path has waited.
 #include "stream_op.h"
 
-#include <new>
-
 namespace qh {
 
 namespace {
@@ -19,7 +17,7 @@ namespace {
 constexpr int kMaxStages = 5;
 
 struct Chain : StreamOp {
-    Chain() : StreamOp(kChainMagic) {}
+    static constexpr OpKind kKind = OpKind::Chain;
     bool msk = false;
     bool offset = false;
     void* stage[kMaxStages] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // PSK: agc, rrc, costas, delay, clock; MSK: fm, clock
@@ -31,8 +29,8 @@ struct Chain : StreamOp {
 };
 
 Chain* as_chain(void* h, bool msk) {
-    Chain* d = static_cast<Chain*>(h);
-    return (d && d->magic == kChainMagic && d->msk == msk) ? d : nullptr;
+    Chain* d = as<Chain>(h);
+    return (d && d->msk == msk) ? d : nullptr;
 }
 
 void* clock_of(const Chain* d) { return d->stage[d->msk ? QDSP_HIP_MSK_CLOCK : QDSP_HIP_PSK_CLOCK]; }
@@ -56,24 +54,21 @@ hipError_t alloc_scratch(Chain* d, long long cap) {
 }
 
 void chain_free(Chain* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    if (d->msk) {
-        qdsp_hip_demod_destroy(d->stage[QDSP_HIP_MSK_FM]);
-        qdsp_hip_mmcr_destroy(d->stage[QDSP_HIP_MSK_CLOCK]);
-    } else {
-        qdsp_hip_cagc_destroy(d->stage[QDSP_HIP_PSK_AGC]);
-        qdsp_hip_rowfir_destroy(d->stage[QDSP_HIP_PSK_RRC]);
-        qdsp_hip_costas_destroy(d->stage[QDSP_HIP_PSK_COSTAS]);
-        qdsp_hip_delay_imag_destroy(d->stage[QDSP_HIP_PSK_DELAY]);
-        qdsp_hip_mmcr_destroy(d->stage[QDSP_HIP_PSK_CLOCK]);
-    }
-    free_scratch(d);
-    if (d->d_counts) (void)hipFree(d->d_counts);
-    if (d->h_count) (void)hipHostFree(d->h_count);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] {
+        if (d->msk) {
+            qdsp_hip_demod_destroy(d->stage[QDSP_HIP_MSK_FM]);
+            qdsp_hip_mmcr_destroy(d->stage[QDSP_HIP_MSK_CLOCK]);
+        } else {
+            qdsp_hip_cagc_destroy(d->stage[QDSP_HIP_PSK_AGC]);
+            qdsp_hip_rowfir_destroy(d->stage[QDSP_HIP_PSK_RRC]);
+            qdsp_hip_costas_destroy(d->stage[QDSP_HIP_PSK_COSTAS]);
+            qdsp_hip_delay_imag_destroy(d->stage[QDSP_HIP_PSK_DELAY]);
+            qdsp_hip_mmcr_destroy(d->stage[QDSP_HIP_PSK_CLOCK]);
+        }
+        free_scratch(d);
+        if (d->d_counts) (void)hipFree(d->d_counts);
+        if (d->h_count) (void)hipHostFree(d->h_count);
+    });
 }
 
 int64_t chain_out_size(const Chain* d, int64_t count) { return qdsp_hip_mmcr_out_size(clock_of(d), count); }
@@ -121,14 +116,11 @@ int chain_launch(Chain* d, const void* d_in, int64_t count, int64_t in_stride, v
 }
 
 // the head of both creates; the stages follow
-int chain_new(Chain** out, void** h, int device, int nchan, int max_block, bool msk, bool offset) {
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    Chain* d = new (std::nothrow) Chain();
-    if (!d) return QDSP_HIP_ENOMEM;
+int chain_new(Chain** out, void** h, bool args_ok, int device, int nchan, int max_block, bool msk, bool offset) {
+    Chain* d = nullptr;
+    if (const int rc = op_new<Chain, chain_launch, chain_out_count>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->msk = msk;
     d->offset = offset;
-    d->launch = launch_as<Chain, chain_launch>;
-    d->out_count = chain_out_count;
     const size_t out_es = msk ? sizeof(float) : 2 * sizeof(float);
     hipError_t err = stream_op_init(d, device, nchan, max_block, 2 * sizeof(float), out_es);
     d->nchan = nchan;
@@ -150,12 +142,7 @@ int chain_finish(Chain* d, int rc, void** h) {
         const hipError_t err = alloc_scratch(d, ((long long)d->max_block + 3) & ~3LL);
         if (err != hipSuccess) rc = -(int)err;
     }
-    if (rc) {
-        chain_free(d);
-        return rc;
-    }
-    *h = d;
-    return 0;
+    return op_created<chain_free>(h, d, rc);
 }
 
 int chain_stage(Chain* d, int which, void** stage) {
@@ -230,10 +217,9 @@ extern "C" {
 
 int qdsp_hip_psk_create(void** h, int device, int order, int offset, int nchan, int max_block, const float* rrc_taps, int ntaps,
                         float agc_rate, float costas_bw, float omega, float gain_omega, float mu_gain, float rel_limit) {
-    if (h) *h = nullptr;
-    if ((order != 2 && order != 4 && order != 8) || (offset != 0 && offset != 1) || !rrc_taps) return QDSP_HIP_EINVAL;
+    const bool args_ok = (order == 2 || order == 4 || order == 8) && (offset == 0 || offset == 1) && rrc_taps;
     Chain* d = nullptr;
-    if (const int rc = chain_new(&d, h, device, nchan, max_block, false, offset != 0)) return rc;
+    if (const int rc = chain_new(&d, h, args_ok, device, nchan, max_block, false, offset != 0)) return rc;
     int rc = qdsp_hip_cagc_create(&d->stage[QDSP_HIP_PSK_AGC], device, nchan, 1);
     if (!rc) rc = qdsp_hip_cagc_set(d->stage[QDSP_HIP_PSK_AGC], -1, 1.0f, 65535, agc_rate);   // PSKDemod::init
     if (!rc) rc = qdsp_hip_rowfir_create(&d->stage[QDSP_HIP_PSK_RRC], device, 1, nchan, rrc_taps, ntaps, 1);
@@ -245,9 +231,8 @@ int qdsp_hip_psk_create(void** h, int device, int order, int offset, int nchan, 
 }
 int qdsp_hip_msk_create(void** h, int device, int nchan, int max_block, float sample_rate, float deviation, float omega,
                         float gain_omega, float mu_gain, float rel_limit) {
-    if (h) *h = nullptr;
     Chain* d = nullptr;
-    if (const int rc = chain_new(&d, h, device, nchan, max_block, true, false)) return rc;
+    if (const int rc = chain_new(&d, h, true, device, nchan, max_block, true, false)) return rc;
     int rc = qdsp_hip_demod_create(&d->stage[QDSP_HIP_MSK_FM], device, QDSP_HIP_DEMOD_FM, nchan, 1);
     if (!rc) rc = qdsp_hip_demod_set_fm(d->stage[QDSP_HIP_MSK_FM], -1, sample_rate, deviation);
     if (!rc) rc = qdsp_hip_mmcr_create(&d->stage[QDSP_HIP_MSK_CLOCK], device, 0, nchan, 1, omega, gain_omega, mu_gain, rel_limit);

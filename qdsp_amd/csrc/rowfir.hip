@@ -136,13 +136,7 @@ size_t sample_bytes(const RowFir* d) { return d->kind ? sizeof(float2) : sizeof(
 size_t hist_bytes(const RowFir* d, int ntaps) { return (size_t)d->nchan * (size_t)(ntaps > 1 ? ntaps - 1 : 1) * sample_bytes(d); }
 
 void rowfir_free(RowFir* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_taps, (void*)d->d_hist[0], (void*)d->d_hist[1]})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_taps, d->d_hist[0], d->d_hist[1]}); });
 }
 
 // `taps`: [nchan][ntaps].  New tap and history buffers when the count changes, the newest min(old, new) - 1 samples of every row
@@ -224,13 +218,7 @@ int rowfir_launch(RowFir* d, const void* d_in, int64_t count, int64_t in_stride,
 }
 
 void delay_free(DelayImagOp* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (unsigned* p : d->d_last)
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] { hip_free_all({d->d_last[0], d->d_last[1]}); });
 }
 
 int delay_launch(DelayImagOp* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s) {
@@ -275,13 +263,10 @@ int qdsp_hip_rowfir_tile(void) { return qk::kRowFirTile; }
 int qdsp_hip_rowfir_tap_group(void) { return qk::kRowFirGroup; }
 
 int qdsp_hip_rowfir_create(void** h, int device, int kind, int nchan, const float* taps, int ntaps, int max_block) {
-    if (h) *h = nullptr;
-    if ((kind != 0 && kind != 1) || !taps_ok(taps, ntaps)) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    RowFir* d = new (std::nothrow) RowFir();
-    if (!d) return QDSP_HIP_ENOMEM;
+    RowFir* d = nullptr;
+    const bool args_ok = (kind == 0 || kind == 1) && taps_ok(taps, ntaps);
+    if (const int rc = op_new<RowFir, rowfir_launch>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
-    d->launch = launch_as<RowFir, rowfir_launch>;
     hipError_t err = stream_op_init(d, device, nchan, max_block, sample_bytes(d), sample_bytes(d));
     d->nchan = nchan;
     if (err == hipSuccess) {
@@ -290,15 +275,10 @@ int qdsp_hip_rowfir_create(void** h, int device, int kind, int nchan, const floa
         err = install_taps(d, all, ntaps);
     }
     if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        rowfir_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<rowfir_free>(h, d, err);
 }
 int qdsp_hip_rowfir_set_taps(void* h, int chan, const float* taps, int ntaps) {
-    RowFir* d = as_rowfir(h);
+    RowFir* d = as<RowFir>(h);
     if (!d || !taps_ok(taps, ntaps) || (chan != -1 && (!chan_ok(d, chan) || ntaps != d->ntaps))) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
@@ -314,55 +294,49 @@ int qdsp_hip_rowfir_set_taps(void* h, int chan, const float* taps, int ntaps) {
     return 0;
 }
 int qdsp_hip_rowfir_ntaps(void* h) {
-    RowFir* d = as_rowfir(h);
+    RowFir* d = as<RowFir>(h);
     return d ? d->ntaps : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rowfir_get_history(void* h, int chan, float* hist) {
-    RowFir* d = as_rowfir(h);
+    RowFir* d = as<RowFir>(h);
     if (!d || !chan_ok(d, chan) || !hist) return QDSP_HIP_EINVAL;
     const size_t row = (size_t)(d->ntaps - 1) * sample_bytes(d);
     if (row == 0) return 0;
     return sync_download(d, hist, reinterpret_cast<char*>(d->d_hist[d->cur]) + (size_t)chan * row, row);
 }
 int qdsp_hip_rowfir_set_history(void* h, int chan, const float* hist) {
-    RowFir* d = as_rowfir(h);
+    RowFir* d = as<RowFir>(h);
     if (!d || !chan_ok(d, chan) || !hist) return QDSP_HIP_EINVAL;
     const size_t row = (size_t)(d->ntaps - 1) * sample_bytes(d);
     if (row == 0) return 0;
     return sync_upload(d, reinterpret_cast<char*>(d->d_hist[d->cur]) + (size_t)chan * row, hist, row);
 }
 int qdsp_hip_rowfir_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    RowFir* d = as_rowfir(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<RowFir>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_rowfir_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_rowfir_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_rowfir_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    RowFir* d = as_rowfir(h);
-    return d ? rowfir_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<RowFir, rowfir_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_rowfir_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                       void* hip_stream) {
-    RowFir* d = as_rowfir(h);
-    return d ? rowfir_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<RowFir, rowfir_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_rowfir_reset(void* h) {
-    RowFir* d = as_rowfir(h);
+    RowFir* d = as<RowFir>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
     for (int i = 0; i < 2; i++) HIPCHK(hipMemset(d->d_hist[i], 0, hist_bytes(d, d->ntaps)));
     return 0;
 }
-void qdsp_hip_rowfir_destroy(void* h) { rowfir_free(as_rowfir(h)); }
+void qdsp_hip_rowfir_destroy(void* h) { rowfir_free(as<RowFir>(h)); }
 
 int qdsp_hip_delay_imag_create(void** h, int device, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    DelayImagOp* d = new (std::nothrow) DelayImagOp();
-    if (!d) return QDSP_HIP_ENOMEM;
-    d->launch = launch_as<DelayImagOp, delay_launch>;
+    DelayImagOp* d = nullptr;
+    if (const int rc = op_new<DelayImagOp, delay_launch>(&d, h, true, device, nchan, max_block)) return rc;
     hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float2), sizeof(float2));
     d->nchan = nchan;
     for (int i = 0; i < 2 && err == hipSuccess; i++) {
@@ -370,20 +344,15 @@ int qdsp_hip_delay_imag_create(void** h, int device, int nchan, int max_block) {
         if (err == hipSuccess) err = hipMemset(d->d_last[i], 0, (size_t)nchan * sizeof(unsigned));
     }
     if (err == hipSuccess) err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        delay_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<delay_free>(h, d, err);
 }
 int qdsp_hip_delay_imag_get_state(void* h, int chan, float* last_im) {
-    DelayImagOp* d = as_delay_imag(h);
+    DelayImagOp* d = as<DelayImagOp>(h);
     if (!d || !chan_ok(d, chan) || !last_im) return QDSP_HIP_EINVAL;
     return sync_download(d, last_im, d->d_last[d->cur] + chan, sizeof(float));
 }
 int qdsp_hip_delay_imag_set_state(void* h, int chan, float last_im) {
-    DelayImagOp* d = as_delay_imag(h);
+    DelayImagOp* d = as<DelayImagOp>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     unsigned bits;
     memcpy(&bits, &last_im, sizeof(bits));
@@ -391,29 +360,26 @@ int qdsp_hip_delay_imag_set_state(void* h, int chan, float last_im) {
     return sync_upload(d, d->d_last[d->cur] + chan_first(chan), w.data(), w.size() * sizeof(unsigned));
 }
 int qdsp_hip_delay_imag_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    DelayImagOp* d = as_delay_imag(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<DelayImagOp>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_delay_imag_process(void* h, const float* in_iq, int count, float* out_iq) {
     return qdsp_hip_delay_imag_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out_iq, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_delay_imag_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    DelayImagOp* d = as_delay_imag(h);
-    return d ? delay_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<DelayImagOp, delay_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_delay_imag_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                           void* hip_stream) {
-    DelayImagOp* d = as_delay_imag(h);
-    return d ? delay_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<DelayImagOp, delay_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_delay_imag_reset(void* h) {
-    DelayImagOp* d = as_delay_imag(h);
+    DelayImagOp* d = as<DelayImagOp>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
     for (int i = 0; i < 2; i++) HIPCHK(hipMemset(d->d_last[i], 0, (size_t)d->nchan * sizeof(unsigned)));
     return 0;
 }
-void qdsp_hip_delay_imag_destroy(void* h) { delay_free(as_delay_imag(h)); }
+void qdsp_hip_delay_imag_destroy(void* h) { delay_free(as<DelayImagOp>(h)); }
 
 }  // extern "C"

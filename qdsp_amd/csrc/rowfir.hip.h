@@ -64,7 +64,7 @@ struct DelayImagArgs {
 namespace qh {
 
 struct RowFir : StreamOp {
-    RowFir() : StreamOp(kRowFirMagic) {}
+    static constexpr OpKind kKind = OpKind::RowFir;
     int kind = 0;                          // 0 float rows, 1 complex_t rows
     int ntaps = 0;
     float* d_taps = nullptr;               // [nchan][ntaps]
@@ -72,19 +72,11 @@ struct RowFir : StreamOp {
     int cur = 0;
     std::vector<float> taps;               // [nchan][ntaps]
 };
-inline RowFir* as_rowfir(void* h) {
-    RowFir* d = static_cast<RowFir*>(h);
-    return (d && d->magic == kRowFirMagic) ? d : nullptr;
-}
 
 struct DelayImagOp : StreamOp {
-    DelayImagOp() : StreamOp(kDelayImagMagic) {}
+    static constexpr OpKind kKind = OpKind::DelayImag;
     unsigned* d_last[2] = {nullptr, nullptr};   // [nchan] lastIm, as bits
     int cur = 0;
 };
-inline DelayImagOp* as_delay_imag(void* h) {
-    DelayImagOp* d = static_cast<DelayImagOp*>(h);
-    return (d && d->magic == kDelayImagMagic) ? d : nullptr;
-}
 
 }  // namespace qh

@@ -309,15 +309,10 @@ bool spans_overlap(const void* p, size_t pn, const void* q, size_t qn) {
 constexpr int64_t kRsMaxFrames = (int64_t)1 << 22;     // per row and call
 
 void rs_free(Rs* d) {
-    if (!d) return;
-    stream_op_unregister(d);
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : {(void*)d->d_tab, (void*)d->d_scratch, (void*)d->d_good, (void*)d->d_slots, (void*)d->d_counts})
-        if (p) (void)hipFree(p);
-    if (d->h_count) (void)hipHostFree(d->h_count);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] {
+        hip_free_all({d->d_tab, d->d_scratch, d->d_good, d->d_slots, d->d_counts});
+        if (d->h_count) (void)hipHostFree(d->h_count);
+    });
 }
 
 // scratch slots, flags and output slots for calls of up to `frames` frames per row (a larger call than any before synchronises)
@@ -440,13 +435,7 @@ int rs_create(void** h, int device, int nchan, int max_block, qrs::Params p, con
         *d->h_count = 0;
         err = hipDeviceSynchronize();
     }
-    if (err != hipSuccess) {
-        rs_free(d);
-        return -(int)err;
-    }
-    stream_op_register(d, kKindRs);
-    *h = d;
-    return 0;
+    return op_created<rs_free>(h, d, err);
 }
 
 }  // namespace
@@ -476,26 +465,26 @@ int qdsp_hip_falcon_rs_create(void** h, int device, int nchan, int max_block) {
     return qdsp_hip_rs_create(h, device, nchan, max_block, qrs::kCcsdsPoly, 120, 11, 16, 5, 4, 1, from_db, to_db, rnd, 255);
 }
 int qdsp_hip_rs_set_maps(void* h, const uint8_t* in_map, const uint8_t* out_map, const uint8_t* xor_seq, int xor_len) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     if (!d || !rs_xor_ok(d, xor_seq, xor_len)) return QDSP_HIP_EINVAL;
     rs_fill_tab(d, in_map, out_map, xor_seq, xor_len);
     return sync_upload(d, d->d_tab, d->tab.data(), d->tab.size());
 }
 int64_t qdsp_hip_rs_out_size(void* h, int64_t nframes) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     return (d && nframes >= 0) ? nframes : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_frame_in_bytes(void* h) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     return d ? d->p.frame_in : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_frame_out_bytes(void* h) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     return d ? d->p.frame_out : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, int64_t in_stride_bytes, const int* d_in_counts, void* d_out,
                                   int64_t out_stride_bytes, int* d_counts, int* d_errs, void* hip_stream) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     if (!d) return QDSP_HIP_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (const int rc = rs_launch_counts(d, d_in, nframes, in_stride_bytes, d_in_counts, d_out, out_stride_bytes, d_errs, s)) return rc;
@@ -503,16 +492,16 @@ int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, in
     return 0;
 }
 int qdsp_hip_rs_process_dev(void* h, const void* d_in, int64_t nframes, void* d_out, void* hip_stream) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     return d ? rs_launch(d, d_in, nframes, nframes, d_out, nframes, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_get_counts(void* h, int* counts) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     if (!d || !counts) return QDSP_HIP_EINVAL;
     return sync_download(d, counts, d->d_counts, (size_t)d->nchan * sizeof(int));
 }
 int qdsp_hip_rs_process_ex(void* h, const void* in, int in_link, int nframes, void* out, int out_link) {
-    Rs* d = as_rs(h);
+    Rs* d = as<Rs>(h);
     // the good-frame count is returned, so the call has to have run: an output link that hands over without waiting cannot be served
     if (!d || (out_link != QDSP_HIP_LINK_HOST && out_link != QDSP_HIP_LINK_DEVICE)) return QDSP_HIP_EINVAL;
     const int64_t rc = stream_op_process_ex(d, in, in_link, nframes, out, out_link);
@@ -522,6 +511,6 @@ int qdsp_hip_rs_process_ex(void* h, const void* in, int in_link, int nframes, vo
 int qdsp_hip_rs_process(void* h, const uint8_t* in, int nframes, uint8_t* out) {
     return qdsp_hip_rs_process_ex(h, in, QDSP_HIP_LINK_HOST, nframes, out, QDSP_HIP_LINK_HOST);
 }
-void qdsp_hip_rs_destroy(void* h) { rs_free(as_rs(h)); }
+void qdsp_hip_rs_destroy(void* h) { rs_free(as<Rs>(h)); }
 
 }  // extern "C"

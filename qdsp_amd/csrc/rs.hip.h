@@ -55,7 +55,7 @@ struct RsArgs {
 namespace qh {
 
 struct Rs : StreamOp {
-    Rs() : StreamOp(0) {}
+    static constexpr OpKind kKind = OpKind::Rs;
     qrs::Params p;
     qrs::Field field;
     std::vector<unsigned char> tab;     // host copy of the device tables
@@ -68,6 +68,5 @@ struct Rs : StreamOp {
     int* d_counts = nullptr;
     int* h_count = nullptr;             // pinned: row 0's count of the last process_ex call
 };
-inline Rs* as_rs(void* h) { return static_cast<Rs*>(stream_op_registered(h, kKindRs)); }
 
 }  // namespace qh

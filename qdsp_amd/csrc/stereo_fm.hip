@@ -135,15 +135,10 @@ void free_scratch(StereoFm* d) {
 }
 
 void sfm_free(StereoFm* d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    free_scratch(d);
-    for (void* p : {(void*)d->d_phase[0], (void*)d->d_phase[1], (void*)d->d_hist[0], (void*)d->d_hist[1], (void*)d->d_level[0],
-                    (void*)d->d_level[1], (void*)d->d_speed, (void*)d->d_cfr, (void*)d->d_taps})
-        if (p) (void)hipFree(p);
-    stream_op_release(d);
-    delete d;
+    op_free(d, [d] {
+        free_scratch(d);
+        hip_free_all({d->d_phase[0], d->d_phase[1], d->d_hist[0], d->d_hist[1], d->d_level[0], d->d_level[1], d->d_speed, d->d_cfr, d->d_taps});
+    });
 }
 
 // rows of `cap` samples (a multiple of 4) for m and f, one partial per tile
@@ -192,12 +187,9 @@ hipError_t load_taps(StereoFm* d, const float* taps, int ntaps) {
 int sfm_launch(StereoFm* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s);
 
 int sfm_new(void** h, int device, int nchan, const float* taps, int ntaps, int max_block) {
-    if (h) *h = nullptr;
-    if (!taps || ntaps < 1 || ntaps > qk::kPilotMaxTaps) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    StereoFm* d = new (std::nothrow) StereoFm();
-    if (!d) return QDSP_HIP_ENOMEM;
-    d->launch = launch_as<StereoFm, sfm_launch>;
+    StereoFm* d = nullptr;
+    const bool args_ok = taps && ntaps >= 1 && ntaps <= qk::kPilotMaxTaps;
+    if (const int rc = op_new<StereoFm, sfm_launch>(&d, h, args_ok, device, nchan, max_block)) return rc;
     // sampleRate == deviation == 1 until set_fm
     d->speed.assign(nchan, (2 * 3.1415926535f) / (1.0f / 1.0f));
     d->cfr.assign(nchan, 20.0f / 1.0f);
@@ -216,12 +208,7 @@ int sfm_new(void** h, int device, int nchan, const float* taps, int ntaps, int m
     if (err == hipSuccess) err = hipMalloc(&d->d_taps, (size_t)qk::kPilotMaxTaps * sizeof(float));
     if (err == hipSuccess) err = load_taps(d, taps, ntaps);
     if (err == hipSuccess && max_block > 0) err = alloc_scratch(d, ((long long)max_block + 3) & ~3LL);
-    if (err != hipSuccess) {
-        sfm_free(d);
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<sfm_free>(h, d, err);
 }
 
 // d_in: nchan rows of `count` complex samples, in_stride apart; d_out: nchan rows of `count` stereo_t, out_stride apart
@@ -310,7 +297,7 @@ int qdsp_hip_stereo_fm_create(void** h, int device, int nchan, const float* pilo
     return sfm_new(h, device, nchan, pilot_taps, ntaps, max_block);
 }
 int qdsp_hip_stereo_fm_set_fm(void* h, int chan, float sample_rate, float deviation) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     // FloatFMDemod::init (demodulator.h:42) and AGC::init's _CorrectedFallRate with fallRate 20 (demodulator.h:219, processing.h:93)
     const float speed = (2 * 3.1415926535f) / (sample_rate / deviation);
@@ -326,7 +313,7 @@ int qdsp_hip_stereo_fm_set_fm(void* h, int chan, float sample_rate, float deviat
     return 0;
 }
 int qdsp_hip_stereo_fm_set_pilot_taps(void* h, const float* taps, int ntaps) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || !taps || ntaps < 1 || ntaps > qk::kPilotMaxTaps) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
@@ -334,50 +321,47 @@ int qdsp_hip_stereo_fm_set_pilot_taps(void* h, const float* taps, int ntaps) {
     return 0;
 }
 int qdsp_hip_stereo_fm_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    StereoFm* d = as_stereo_fm(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<StereoFm>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_stereo_fm_process(void* h, const float* in_iq, int count, float* out_lr) {
     return qdsp_hip_stereo_fm_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out_lr, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_stereo_fm_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    StereoFm* d = as_stereo_fm(h);
-    return d ? sfm_launch(d, d_in, count, count, d_out, count, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_dev<StereoFm, sfm_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_stereo_fm_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                          void* hip_stream) {
-    StereoFm* d = as_stereo_fm(h);
-    return d ? sfm_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<StereoFm, sfm_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_stereo_fm_get_phase(void* h, int chan, float* phase) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || !chan_ok(d, chan) || !phase) return QDSP_HIP_EINVAL;
     return get_word(d, d->d_phase, chan, phase);
 }
 int qdsp_hip_stereo_fm_set_phase(void* h, int chan, float phase) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     return set_word(d, d->d_phase, chan, phase);
 }
 int qdsp_hip_stereo_fm_get_level(void* h, int chan, float* level) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || !chan_ok(d, chan) || !level) return QDSP_HIP_EINVAL;
     return get_word(d, d->d_level, chan, level);
 }
 int qdsp_hip_stereo_fm_set_level(void* h, int chan, float level) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     return set_word(d, d->d_level, chan, level);
 }
 int qdsp_hip_stereo_fm_pilot_dev(void* h, void** d_pilot, int64_t* stride) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d || !d_pilot || !stride) return QDSP_HIP_EINVAL;
     *d_pilot = d->last_count > 0 ? d->d_f : nullptr;
     *stride = d->last_sstride;
     return 0;
 }
 int qdsp_hip_stereo_fm_reset(void* h) {
-    StereoFm* d = as_stereo_fm(h);
+    StereoFm* d = as<StereoFm>(h);
     if (!d) return QDSP_HIP_EINVAL;
     HIPCHK(hipSetDevice(d->device));
     HIPCHK(hipDeviceSynchronize());
@@ -388,6 +372,6 @@ int qdsp_hip_stereo_fm_reset(void* h) {
     }
     return 0;
 }
-void qdsp_hip_stereo_fm_destroy(void* h) { sfm_free(as_stereo_fm(h)); }
+void qdsp_hip_stereo_fm_destroy(void* h) { sfm_free(as<StereoFm>(h)); }
 
 }  // extern "C"

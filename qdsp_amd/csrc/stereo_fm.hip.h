@@ -58,7 +58,7 @@ struct MixArgs {
 namespace qh {
 
 struct StereoFm : StreamOp {
-    StereoFm() : StreamOp(kStereoFmMagic) {}
+    static constexpr OpKind kKind = OpKind::StereoFm;
     int ntaps = 0;
     float* d_phase[2] = {nullptr, nullptr};   // FM phase, history and level: read from slot cur, written to cur ^ 1
     float* d_hist[2] = {nullptr, nullptr};
@@ -74,9 +74,5 @@ struct StereoFm : StreamOp {
     long long scratch_cap = 0;             // samples per row
     long long last_count = 0, last_sstride = 0;
 };
-inline StereoFm* as_stereo_fm(void* h) {
-    StereoFm* d = static_cast<StereoFm*>(h);
-    return (d && d->magic == kStereoFmMagic) ? d : nullptr;
-}
 
 }  // namespace qh

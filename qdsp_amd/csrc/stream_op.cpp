@@ -6,6 +6,7 @@
 
 #include <chrono>
 #include <mutex>
+#include <shared_mutex>
 #include <unordered_map>
 
 namespace qh {
@@ -75,45 +76,42 @@ void* mapped_host_ptr(void* p) {
 
 namespace {
 struct Registry {
-    std::mutex m;
-    std::unordered_map<void*, int> live;    // handle -> kind
+    std::shared_mutex m;
+    std::unordered_map<const void*, OpKind> live;    // handle -> kind
 };
 Registry& registry() {
     static Registry* r = new Registry();    // (never destroyed: a handle may be released from a static destructor)
     return *r;
 }
+// h if it is in the table and `ok` takes its kind; h itself is not read
+template <class F>
+StreamOp* lookup(void* h, F ok) {
+    if (!h) return nullptr;
+    Registry& r = registry();
+    std::shared_lock<std::shared_mutex> lk(r.m);
+    const auto it = r.live.find(h);
+    return (it != r.live.end() && ok(it->second)) ? static_cast<StreamOp*>(h) : nullptr;
+}
 }  // namespace
 
-void stream_op_register(StreamOp* d, int kind) {
+void stream_op_register(StreamOp* d, OpKind kind) {
     Registry& r = registry();
-    std::lock_guard<std::mutex> lk(r.m);
+    std::unique_lock<std::shared_mutex> lk(r.m);
     r.live[d] = kind;
 }
 
 void stream_op_unregister(StreamOp* d) {
     Registry& r = registry();
-    std::lock_guard<std::mutex> lk(r.m);
+    std::unique_lock<std::shared_mutex> lk(r.m);
     r.live.erase(d);
 }
 
-StreamOp* stream_op_registered(void* h, int kind) {
-    if (!h) return nullptr;
-    Registry& r = registry();
-    std::lock_guard<std::mutex> lk(r.m);
-    const auto it = r.live.find(h);
-    if (it == r.live.end() || (kind != 0 && it->second != kind)) return nullptr;
-    return static_cast<StreamOp*>(h);
+StreamOp* stream_op_lookup(void* h, OpKind kind) {
+    return lookup(h, [kind](OpKind k) { return k == kind; });
 }
 
 StreamOp* as_stream_op(void* h) {
-    StreamOp* d = static_cast<StreamOp*>(h);
-    if (!d) return nullptr;
-    switch (d->magic) {
-        case kDemodMagic: case kDeempMagic: case kLevelMagic: case kStereoFmMagic: case kFfAgcMagic: case kCagcMagic: case kCostasMagic:
-        case kMmcrMagic: case kRowFirMagic: case kDelayImagMagic: case kChainMagic:
-            return d;
-    }
-    return stream_op_registered(h, 0);      // (the kinds without a magic; nothing changes for the eleven above)
+    return lookup(h, [](OpKind) { return true; });
 }
 
 int stream_op_check(void** h, int device, int nchan, int max_block) {
@@ -149,7 +147,6 @@ void stream_op_release(StreamOp* d) {
     d->d_in = d->d_out = nullptr;
     d->ev0 = d->ev1 = nullptr;
     d->stream = d->last_stream = nullptr;
-    d->magic = 0;
 }
 
 int64_t stream_op_process_ex(StreamOp* d, const void* in, int in_link, int count, void* out, int out_link) {

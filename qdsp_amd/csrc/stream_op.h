@@ -1,13 +1,16 @@
 // stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr /
 // rowfir / deframe / rs .hip, psk_chain.cpp):
-// the head of the handle, its creation and release, and the one block-graph path (*_process_ex) and timing loop behind all of
-// them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
+// the head of the handle, the table that tells live handles and their kinds apart, the shape of create / free / the forwarding
+// entry points, and the one block-graph path (*_process_ex) and timing loop behind all of them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
 #pragma once
 #include "../../include/qdsp_hip.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <initializer_list>
+#include <new>
 
 namespace qh {
 
@@ -22,22 +25,29 @@ struct Launch {
     int grid = 0, block = 0, lds = 0;
 };
 
-constexpr uint32_t kDemodMagic = 0x51444d44u;     // "QDMD"  demod.hip.h
-constexpr uint32_t kDeempMagic = 0x51444545u;     // "QDEE"  deemp.hip.h
-constexpr uint32_t kLevelMagic = 0x514c564cu;     // "QLVL"  level.hip.h
-constexpr uint32_t kStereoFmMagic = 0x5153464du;  // "QSFM"  stereo_fm.hip.h
-constexpr uint32_t kFfAgcMagic = 0x51464147u;     // "QFAG"  ff_agc.hip.h
-constexpr uint32_t kCagcMagic = 0x51434147u;      // "QCAG"  cagc.hip.h
-constexpr uint32_t kCostasMagic = 0x51434f53u;    // "QCOS"  costas.hip.h
-constexpr uint32_t kMmcrMagic = 0x514d4d43u;      // "QMMC"  mmcr.hip.h
-constexpr uint32_t kRowFirMagic = 0x51524649u;    // "QRFI"  rowfir.hip.h
-constexpr uint32_t kDelayImagMagic = 0x5144494du; // "QDIM"  rowfir.hip.h
-constexpr uint32_t kChainMagic = 0x5150534bu;     // "QPSK"  psk_chain.cpp (PSKDemod and MSKDemod chains)
 constexpr int kDemodMaxChan = 65535;              // grid.y
 
-// The head of every per-row handle.  No virtual functions: every as_* reads `magic` at offset 0 of a handle of unknown kind.
+// The kinds of per-row handle; every handle struct names its own as `static constexpr OpKind kKind`.
+enum class OpKind : int {
+    Demod = 1,     // demod.hip.h (FM, FM stereo, AM; SSB is a sub-kind)
+    Deemp,         // deemp.hip.h
+    Level,         // level.hip.h (Squelch and AGC are sub-kinds)
+    StereoFm,      // stereo_fm.hip.h
+    FfAgc,         // ff_agc.hip.h
+    Cagc,          // cagc.hip.h
+    Costas,        // costas.hip.h
+    Mmcr,          // mmcr.hip.h
+    RowFir,        // rowfir.hip.h
+    DelayImag,     // rowfir.hip.h
+    Chain,         // psk_chain.cpp (PSKDemod and MSKDemod are sub-kinds)
+    Threshold,     // deframe.hip.h
+    Deframer,      // deframe.hip.h
+    Rs,            // rs.hip.h: the Reed-Solomon decoder and its FalconRS preset
+};
+constexpr OpKind kLastOpKind = OpKind::Rs;
+
+// The head of every per-row handle.  No virtual functions, and nothing in it says what the handle is: that is the table's to say.
 struct StreamOp {
-    uint32_t magic;
     int device = 0;
     int nchan = 1;
     hipStream_t stream = nullptr;          // host-pointer path
@@ -53,8 +63,6 @@ struct StreamOp {
     // process_ex returns (0, or FeedForwardAGC's output count).
     int64_t (*launch)(StreamOp*, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t s) = nullptr;
     int64_t (*out_count)(const StreamOp*, int64_t count) = nullptr;   // outputs of the next call of `count` samples; null: count
-
-    explicit StreamOp(uint32_t m) : magic(m) {}
 };
 
 // `launch` for an operator whose own launch function takes its handle type
@@ -63,37 +71,96 @@ int64_t launch_as(StreamOp* op, const void* d_in, int64_t count, int64_t in_stri
     return F(static_cast<T*>(op), d_in, count, in_stride, d_out, out_stride, s);
 }
 
-// Kinds without a magic (deframe.hip.h: Threshold, Deframer).  Why two of thirteen kinds are told apart differently: the eleven magics
-// above are a closed set -- tests/test_psk_cpu.py counts the k*Magic constants of this header and checks that they differ, and a
-// feature may not edit an existing test -- so a kind added after them cannot bring a twelfth constant.  Such a handle has magic 0,
-// which no as_* of a kind above takes, and is known by its address instead: it is entered in a table (a mutex and a hash map in
-// stream_op.cpp, alive for the whole process) under its kind at create and taken out at destroy.  as_threshold / as_deframer only
-// look the pointer up, so they refuse a stale or foreign pointer without reading it.  as_stream_op (last_kernel, set_done_event,
-// time_process_dev) still reads `magic` of an unknown pointer first, as it always has; the table is only asked, and its lock only
-// taken, for a handle that is none of the eleven.
-constexpr int kKindThreshold = 1;
-constexpr int kKindDeframer = 2;
-constexpr int kKindRs = 3;               // rs.hip.h: the Reed-Solomon decoder and its FalconRS preset
-void stream_op_register(StreamOp* d, int kind);
-void stream_op_unregister(StreamOp* d);
-// h if it is a live registered handle of `kind` (0: of any kind)
-StreamOp* stream_op_registered(void* h, int kind);
-
-// h if it is one of the kinds above (by magic, no lock), or else a registered handle
+// How a per-row handle is known: by its address.  A table (a reader-writer lock and a hash map in stream_op.cpp, alive for the
+// whole process) holds every live handle under its kind, entered as the last step of a successful create and taken out as the
+// first step of its free.  A lookup never reads the caller's pointer: a destroyed handle, a second destroy and foreign memory are
+// refused whatever they hold.  Lookups share the lock; only register and unregister exclude.
+// (The engine, channelizer, math and ring handles -- kMagic, kChanMagic, kMathMagic, kRingMagic -- are no StreamOps and keep their magics.)
+void stream_op_register(StreamOp* d, OpKind kind);
+void stream_op_unregister(StreamOp* d);    // (a handle that is not in the table: nothing happens)
+// h if it is a live handle of `kind`
+StreamOp* stream_op_lookup(void* h, OpKind kind);
+// h if it is a live handle of any kind
 StreamOp* as_stream_op(void* h);
+// h as a T if it is a live handle of T's kind.  (Demod, Level and Chain check their sub-kind after it.)
+template <class T>
+T* as(void* h) {
+    return static_cast<T*>(stream_op_lookup(h, T::kKind));
+}
 
 // The argument checks every create begins with, after the operator's own: QDSP_HIP_EINVAL (h, nchan, max_block), then
 // QDSP_HIP_ENODEV, then the device is made current.
 int stream_op_check(void** h, int device, int nchan, int max_block);
 // The stream, the two events and the staging buffers.  On failure nothing is left allocated.
 hipError_t stream_op_init(StreamOp* d, int device, int nchan, int max_block, size_t in_es, size_t out_es);
-// Frees what stream_op_init made and clears the magic (the device is current and idle)
+// Frees what stream_op_init made (the device is current and idle)
 void stream_op_release(StreamOp* d);
 
 // run() with each side on the host or the device (QDSP_HIP_LINK_* codes); one channel.  Returns what d->launch returned.
 int64_t stream_op_process_ex(StreamOp* d, const void* in, int in_link, int count, void* out, int out_link);
 // Mean ms of `iters` back-to-back launches over nchan rows of `count` samples, back to back, on `stream`
 int stream_op_time(StreamOp* d, const void* d_in, int64_t count, void* d_out, void* stream, int iters, float* ms);
+
+// ---- the shape every unit's create, free and forwarding entry points share ----
+// The head of a create: *h nulled, the operator's own argument checks (`args_ok`), stream_op_check, a new T with its launch
+// function (and its output count, where it has one) wired.
+template <class T, auto L, int64_t (*OC)(const StreamOp*, int64_t) = nullptr>
+int op_new(T** d, void** h, bool args_ok, int device, int nchan, int max_block) {
+    if (h) *h = nullptr;
+    if (!args_ok) return QDSP_HIP_EINVAL;
+    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
+    *d = new (std::nothrow) T();
+    if (!*d) return QDSP_HIP_ENOMEM;
+    (*d)->launch = launch_as<T, L>;
+    (*d)->out_count = OC;
+    return 0;
+}
+// The tail of a create: rc == 0 makes d a handle and hands it out; anything else frees it with the unit's free and is returned.
+template <auto Free, class T>
+int op_created(void** h, T* d, int rc) {
+    if (rc) {
+        Free(d);
+        return rc;
+    }
+    stream_op_register(d, T::kKind);
+    *h = d;
+    return 0;
+}
+template <auto Free, class T>
+int op_created(void** h, T* d, hipError_t err) {
+    return op_created<Free>(h, d, -(int)err);
+}
+// A unit's free: `releases` frees what the unit itself allocated, on an idle device
+template <class T, class R>
+void op_free(T* d, R releases) {
+    if (!d) return;
+    stream_op_unregister(d);
+    (void)hipSetDevice(d->device);
+    (void)hipDeviceSynchronize();
+    releases();
+    stream_op_release(d);
+    delete d;
+}
+// (for `releases`: hipFree of every pointer of the list that is set)
+inline void hip_free_all(std::initializer_list<void*> ptrs) {
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+}
+// The forwarding entry points of an operator with as many outputs as inputs.  `As`: the lookup, where the unit has sub-kinds.
+template <class T, T* (*As)(void*) = as<T>>
+int op_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
+    T* d = As(h);
+    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+}
+template <class T, auto L, T* (*As)(void*) = as<T>>
+int op_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, void* hip_stream) {
+    T* d = As(h);
+    return d ? L(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+}
+template <class T, auto L, T* (*As)(void*) = as<T>>
+int op_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
+    return op_process_batch_dev<T, L, As>(h, d_in, count, count, d_out, count, hip_stream);
+}
 
 inline bool chan_ok(const StreamOp* d, int chan) { return chan >= 0 && chan < d->nchan; }
 // chan, or all channels for chan == -1: the first one and how many

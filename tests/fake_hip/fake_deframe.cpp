@@ -16,11 +16,8 @@ using namespace qh;
 namespace {
 
 struct FakeThreshold : StreamOp {
-    FakeThreshold() : StreamOp(0) {}
+    static constexpr OpKind kKind = OpKind::Threshold;
 };
-FakeThreshold* as_thr(void* h) {
-    return static_cast<FakeThreshold*>(stream_op_registered(h, kKindThreshold));
-}
 
 int64_t thr_launch(FakeThreshold* d, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride, hipStream_t) {
     if (count < 0 || in_stride < count || out_stride < count || (count > 0 && (!d_in || !d_out || d_in == d_out))) return QDSP_HIP_EINVAL;
@@ -31,15 +28,15 @@ int64_t thr_launch(FakeThreshold* d, const void* d_in, int64_t count, int64_t in
 }
 
 struct FakeDeframer : StreamOp {
-    FakeDeframer() : StreamOp(0) {}
+    static constexpr OpKind kKind = OpKind::Deframer;
     int kind = 0, frame_len = 1, frame_bytes = 1;
     std::vector<uint8_t> sync, tail, cur;
     int bits_read = -1, bad = 5;
     bool after = false;
     int last_count = 0;
 };
-FakeDeframer* as_df(void* h) {
-    return static_cast<FakeDeframer*>(stream_op_registered(h, kKindDeframer));
+template <class T> void drop(T* d) {
+    op_free(d, [] {});
 }
 
 int64_t out_size_of(const FakeDeframer* d, int64_t count) { return count <= 0 ? 0 : (count + d->frame_len - 1) / d->frame_len; }
@@ -107,30 +104,19 @@ void df_reset(FakeDeframer* d) {
 extern "C" {
 
 int qdsp_hip_threshold_create(void** h, int device, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (nchan != 1) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    FakeThreshold* d = new (std::nothrow) FakeThreshold();
-    if (!d) return QDSP_HIP_ENOMEM;
-    d->launch = launch_as<FakeThreshold, thr_launch>;
-    if (const hipError_t err = stream_op_init(d, device, nchan, max_block, sizeof(float), 1)) {
-        delete d;
-        return -(int)err;
-    }
-    stream_op_register(d, kKindThreshold);
-    *h = d;
-    return 0;
+    FakeThreshold* d = nullptr;
+    if (const int rc = op_new<FakeThreshold, thr_launch>(&d, h, nchan == 1, device, nchan, max_block)) return rc;
+    return op_created<drop<FakeThreshold>>(h, d, stream_op_init(d, device, nchan, max_block, sizeof(float), 1));
 }
 int qdsp_hip_threshold_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    FakeThreshold* d = as_thr(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<FakeThreshold>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_threshold_process(void* h, const float* in, int count, uint8_t* out) {
     return qdsp_hip_threshold_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_threshold_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, const int* d_in_counts, void* d_out,
                                          int64_t out_stride, void* hip_stream) {
-    FakeThreshold* d = as_thr(h);
+    FakeThreshold* d = as<FakeThreshold>(h);
     if (!d) return QDSP_HIP_EINVAL;
     const int64_t n = d_in_counts ? (d_in_counts[0] < 0 ? 0 : (d_in_counts[0] < count ? d_in_counts[0] : count)) : count;
     if (in_stride < count || out_stride < count) return QDSP_HIP_EINVAL;
@@ -139,51 +125,34 @@ int qdsp_hip_threshold_process_batch_dev(void* h, const void* d_in, int64_t coun
 int qdsp_hip_threshold_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
     return qdsp_hip_threshold_process_batch_dev(h, d_in, count, count, nullptr, d_out, count, hip_stream);
 }
-void qdsp_hip_threshold_destroy(void* h) {
-    FakeThreshold* d = as_thr(h);
-    if (!d) return;
-    stream_op_unregister(d);
-    stream_op_release(d);
-    delete d;
-}
+void qdsp_hip_threshold_destroy(void* h) { drop(as<FakeThreshold>(h)); }
 int qdsp_hip_threshold_span(void) { return 4096; }
 
 int qdsp_hip_deframer_create(void** h, int device, int kind, int nchan, int max_block, int frame_len, const uint8_t* sync, int sync_len) {
-    if (h) *h = nullptr;
-    if ((kind != 0 && kind != 1) || nchan != 1 || frame_len < 1 || frame_len > (1 << 20) || !sync || sync_len < 1 || sync_len > 256) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    FakeDeframer* d = new (std::nothrow) FakeDeframer();
-    if (!d) return QDSP_HIP_ENOMEM;
+    FakeDeframer* d = nullptr;
+    const bool args_ok = (kind == 0 || kind == 1) && nchan == 1 && frame_len >= 1 && frame_len <= (1 << 20) && sync && sync_len >= 1 && sync_len <= 256;
+    if (const int rc = op_new<FakeDeframer, df_launch, out_count>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
     d->frame_len = frame_len;
     d->frame_bytes = (frame_len + 7) / 8;
     d->sync.assign(sync, sync + sync_len);
     df_reset(d);
-    d->launch = launch_as<FakeDeframer, df_launch>;
-    d->out_count = out_count;
     hipError_t err = stream_op_init(d, device, nchan, max_block, kind ? sizeof(float) : 1, 1);
     if (err == hipSuccess && max_block > 0) {
         (void)hipFree(d->d_out);
         d->d_out = nullptr;
         err = hipMalloc(&d->d_out, (size_t)out_count(d, max_block));
-        if (err != hipSuccess) stream_op_release(d);
     }
-    if (err != hipSuccess) {
-        delete d;
-        return -(int)err;
-    }
-    stream_op_register(d, kKindDeframer);
-    *h = d;
-    return 0;
+    return op_created<drop<FakeDeframer>>(h, d, err);
 }
 int qdsp_hip_deframer_set_sync(void* h, const uint8_t* sync, int sync_len) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d || !sync || sync_len != (int)d->sync.size()) return QDSP_HIP_EINVAL;
     d->sync.assign(sync, sync + sync_len);
     return 0;
 }
 int qdsp_hip_deframer_get_state(void* h, int chan, int* bits_read, int* bad, int* after) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d || chan != 0 || !bits_read || !bad || !after) return QDSP_HIP_EINVAL;
     *bits_read = d->bits_read;
     *bad = d->bad;
@@ -191,7 +160,7 @@ int qdsp_hip_deframer_get_state(void* h, int chan, int* bits_read, int* bad, int
     return 0;
 }
 int qdsp_hip_deframer_set_state(void* h, int chan, int bits_read, int bad, int after) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d || (chan != -1 && chan != 0) || bits_read < -1 || bits_read >= d->frame_len || bad < 0 || bad > 5 || (after != 0 && after != 1) ||
         (bits_read >= 0 && after))
         return QDSP_HIP_EINVAL;
@@ -201,16 +170,16 @@ int qdsp_hip_deframer_set_state(void* h, int chan, int bits_read, int bad, int a
     return 0;
 }
 int64_t qdsp_hip_deframer_out_size(void* h, int64_t count) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     return (d && count >= 0) ? out_size_of(d, count) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deframer_frame_bytes(void* h) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     return d ? d->frame_bytes : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deframer_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, const int* d_in_counts, void* d_out,
                                         int64_t out_stride_bytes, int* d_counts, void* hip_stream) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d || count < 0 || in_stride < count || out_stride_bytes < out_count(d, count)) return QDSP_HIP_EINVAL;
     const int64_t n = d_in_counts ? (d_in_counts[0] < 0 ? 0 : (d_in_counts[0] < count ? d_in_counts[0] : count)) : count;
     d->last_count = 0;
@@ -219,17 +188,17 @@ int qdsp_hip_deframer_process_batch_dev(void* h, const void* d_in, int64_t count
     return rc;
 }
 int qdsp_hip_deframer_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     return d ? qdsp_hip_deframer_process_batch_dev(h, d_in, count, count, nullptr, d_out, out_count(d, count), nullptr, hip_stream) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_deframer_get_counts(void* h, int* counts) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d || !counts) return QDSP_HIP_EINVAL;
     counts[0] = d->last_count;
     return 0;
 }
 int qdsp_hip_deframer_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d || (out_link != QDSP_HIP_LINK_HOST && out_link != QDSP_HIP_LINK_DEVICE)) return QDSP_HIP_EINVAL;
     const int64_t rc = stream_op_process_ex(d, in, in_link, count, out, out_link);
     if (rc < 0 || count == 0) return (int)rc;
@@ -239,18 +208,12 @@ int qdsp_hip_deframer_process(void* h, const void* in, int count, uint8_t* out) 
     return qdsp_hip_deframer_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_deframer_reset(void* h) {
-    FakeDeframer* d = as_df(h);
+    FakeDeframer* d = as<FakeDeframer>(h);
     if (!d) return QDSP_HIP_EINVAL;
     df_reset(d);
     return 0;
 }
-void qdsp_hip_deframer_destroy(void* h) {
-    FakeDeframer* d = as_df(h);
-    if (!d) return;
-    stream_op_unregister(d);
-    stream_op_release(d);
-    delete d;
-}
+void qdsp_hip_deframer_destroy(void* h) { drop(as<FakeDeframer>(h)); }
 int qdsp_hip_deframer_tile(void) { return 1024; }
 int qdsp_hip_deframer_pack_span(void) { return 2048; }
 

@@ -8,25 +8,18 @@
 #include <math.h>
 #include <string.h>
 
-#include <new>
-
 using namespace qh;
 
 namespace {
 
 struct FakeMmcr : StreamOp {
-    FakeMmcr() : StreamOp(kMmcrMagic) {}
+    static constexpr OpKind kKind = OpKind::Mmcr;
     int kind = 0;
     float omega = 2.0f, gain_omega = 0.0f, mu_gain = 0.0f, rel = 0.0f;
     int64_t next = 0;          // samples from the start of the next call to the next symbol
     int last_count = 0;
     float taps[1032] = {};
 };
-
-FakeMmcr* as_fake(void* h) {
-    FakeMmcr* d = static_cast<FakeMmcr*>(h);
-    return (d && d->magic == kMmcrMagic) ? d : nullptr;
-}
 
 bool rule(float omega, float gain_omega, float mu_gain, float rel) {
     if (!isfinite(omega) || !isfinite(gain_omega) || !isfinite(mu_gain) || !isfinite(rel)) return false;
@@ -55,6 +48,10 @@ int64_t fake_launch(FakeMmcr* d, const void* d_in, int64_t count, int64_t in_str
     return 0;
 }
 
+void drop(FakeMmcr* d) {
+    op_free(d, [] {});
+}
+
 int set(FakeMmcr* d, int chan, float omega, float gain_omega, float mu_gain, float rel) {
     if (!d || (chan != -1 && chan != 0) || !rule(omega, gain_omega, mu_gain, rel)) return QDSP_HIP_EINVAL;
     d->omega = omega;
@@ -70,37 +67,28 @@ extern "C" {
 
 int qdsp_hip_mmcr_create(void** h, int device, int kind, int nchan, int max_block, float omega, float gain_omega, float mu_gain,
                          float rel_limit) {
-    if (h) *h = nullptr;
-    if ((kind != 0 && kind != 1) || nchan != 1 || !rule(omega, gain_omega, mu_gain, rel_limit)) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    FakeMmcr* d = new (std::nothrow) FakeMmcr();
-    if (!d) return QDSP_HIP_ENOMEM;
+    FakeMmcr* d = nullptr;
+    const bool args_ok = (kind == 0 || kind == 1) && nchan == 1 && rule(omega, gain_omega, mu_gain, rel_limit);
+    if (const int rc = op_new<FakeMmcr, fake_launch, out_count>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->kind = kind;
-    d->launch = launch_as<FakeMmcr, fake_launch>;
-    d->out_count = out_count;
     (void)set(d, 0, omega, gain_omega, mu_gain, rel_limit);
     const size_t es = kind ? 8 : 4;
-    if (const hipError_t err = stream_op_init(d, device, nchan, max_block, es, es)) {
-        delete d;
-        return -(int)err;
-    }
-    *h = d;
-    return 0;
+    return op_created<drop>(h, d, stream_op_init(d, device, nchan, max_block, es, es));
 }
 int qdsp_hip_mmcr_set_omega(void* h, int chan, float omega) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     return d ? set(d, chan, omega, d->gain_omega, d->mu_gain, d->rel) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_set_gains(void* h, int chan, float gain_omega, float mu_gain) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     return d ? set(d, chan, d->omega, gain_omega, mu_gain, d->rel) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_set_limit(void* h, int chan, float rel_limit) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     return d ? set(d, chan, d->omega, d->gain_omega, d->mu_gain, rel_limit) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_get_state(void* h, int chan, float* mu, float* dyn_omega, int* next) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d || chan != 0 || !mu || !dyn_omega || !next) return QDSP_HIP_EINVAL;
     *mu = 0.5f;
     *dyn_omega = d->omega;
@@ -108,47 +96,47 @@ int qdsp_hip_mmcr_get_state(void* h, int chan, float* mu, float* dyn_omega, int*
     return 0;
 }
 int qdsp_hip_mmcr_set_state(void* h, int chan, float mu, float dyn_omega, int next) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d || (chan != -1 && chan != 0) || !(mu >= 0.0f && mu < 1.0f) || !isfinite(dyn_omega) || next < 0) return QDSP_HIP_EINVAL;
     d->next = next;
     return 0;
 }
 int64_t qdsp_hip_mmcr_out_size(void* h, int64_t count) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     return (d && count >= 0) ? out_size_of(d, count) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_get_interp_taps(void* h, float* taps) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d || !taps) return QDSP_HIP_EINVAL;
     memcpy(taps, d->taps, sizeof(d->taps));
     return 0;
 }
 int qdsp_hip_mmcr_set_interp_taps(void* h, const float* taps) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d || !taps) return QDSP_HIP_EINVAL;
     memcpy(d->taps, taps, sizeof(d->taps));
     return 0;
 }
 int qdsp_hip_mmcr_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                     int* d_counts, void* hip_stream) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d) return QDSP_HIP_EINVAL;
     const int rc = (int)fake_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream));
     if (rc == 0 && d_counts) d_counts[0] = d->last_count;
     return rc;
 }
 int qdsp_hip_mmcr_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     return d ? qdsp_hip_mmcr_process_batch_dev(h, d_in, count, count, d_out, out_size_of(d, count), nullptr, hip_stream) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_mmcr_get_counts(void* h, int* counts) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d || !counts) return QDSP_HIP_EINVAL;
     counts[0] = d->last_count;
     return 0;
 }
 int qdsp_hip_mmcr_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d || (out_link != QDSP_HIP_LINK_HOST && out_link != QDSP_HIP_LINK_DEVICE)) return QDSP_HIP_EINVAL;
     const int64_t rc = stream_op_process_ex(d, in, in_link, count, out, out_link);
     if (rc < 0 || count == 0) return (int)rc;
@@ -158,17 +146,12 @@ int qdsp_hip_mmcr_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_mmcr_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_mmcr_reset(void* h) {
-    FakeMmcr* d = as_fake(h);
+    FakeMmcr* d = as<FakeMmcr>(h);
     if (!d) return QDSP_HIP_EINVAL;
     d->next = 0;
     d->last_count = 0;
     return 0;
 }
-void qdsp_hip_mmcr_destroy(void* h) {
-    FakeMmcr* d = as_fake(h);
-    if (!d) return;
-    stream_op_release(d);
-    delete d;
-}
+void qdsp_hip_mmcr_destroy(void* h) { drop(as<FakeMmcr>(h)); }
 
 }  // extern "C"

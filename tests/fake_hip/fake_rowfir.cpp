@@ -10,7 +10,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
 using namespace qh;
@@ -18,25 +17,17 @@ using namespace qh;
 namespace {
 
 struct FakeRowFir : StreamOp {
-    FakeRowFir() : StreamOp(kRowFirMagic) {}
+    static constexpr OpKind kKind = OpKind::RowFir;
     int nc = 1;                         // floats per sample
     int ntaps = 0;
     std::vector<float> taps;            // [nchan][ntaps]
     std::vector<float> hist;            // [nchan][ntaps - 1] samples
 };
-FakeRowFir* as_fir(void* h) {
-    FakeRowFir* d = static_cast<FakeRowFir*>(h);
-    return (d && d->magic == kRowFirMagic) ? d : nullptr;
-}
 
 struct FakeDelay : StreamOp {
-    FakeDelay() : StreamOp(kDelayImagMagic) {}
+    static constexpr OpKind kKind = OpKind::DelayImag;
     std::vector<float> last;            // [nchan]
 };
-FakeDelay* as_delay(void* h) {
-    FakeDelay* d = static_cast<FakeDelay*>(h);
-    return (d && d->magic == kDelayImagMagic) ? d : nullptr;
-}
 
 bool spans_overlap(const void* a, int64_t a_stride, const void* b, int64_t b_stride, int nchan, int64_t count, size_t es) {
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((uintptr_t)(nchan - 1) * a_stride + count) * es;
@@ -96,9 +87,7 @@ void install(FakeRowFir* d, const std::vector<float>& taps, int ntaps) {
 }
 
 template <class T> void drop(T* d) {
-    if (!d) return;
-    stream_op_release(d);
-    delete d;
+    op_free(d, [] {});
 }
 
 }  // namespace
@@ -135,25 +124,20 @@ int qdsp_hip_demod_reset(void* h) { return qdsp_hip_demod_process_ex(h, nullptr,
 int qdsp_hip_rowfir_tile(void) { return 2048; }
 int qdsp_hip_rowfir_tap_group(void) { return 12; }
 int qdsp_hip_rowfir_create(void** h, int device, int kind, int nchan, const float* taps, int ntaps, int max_block) {
-    if (h) *h = nullptr;
-    if ((kind != 0 && kind != 1) || !taps || ntaps < 1 || ntaps > 4096) return QDSP_HIP_EINVAL;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    FakeRowFir* d = new (std::nothrow) FakeRowFir();
-    if (!d) return QDSP_HIP_ENOMEM;
+    FakeRowFir* d = nullptr;
+    const bool args_ok = (kind == 0 || kind == 1) && taps && ntaps >= 1 && ntaps <= 4096;
+    if (const int rc = op_new<FakeRowFir, fir_launch>(&d, h, args_ok, device, nchan, max_block)) return rc;
     d->nc = kind ? 2 : 1;
-    d->launch = launch_as<FakeRowFir, fir_launch>;
-    if (const hipError_t err = stream_op_init(d, device, nchan, max_block, d->nc * sizeof(float), d->nc * sizeof(float))) {
-        delete d;
-        return -(int)err;
+    const hipError_t err = stream_op_init(d, device, nchan, max_block, d->nc * sizeof(float), d->nc * sizeof(float));
+    if (err == hipSuccess) {
+        std::vector<float> all((size_t)nchan * ntaps);
+        for (int c = 0; c < nchan; c++) memcpy(&all[(size_t)c * ntaps], taps, (size_t)ntaps * sizeof(float));
+        install(d, all, ntaps);
     }
-    std::vector<float> all((size_t)nchan * ntaps);
-    for (int c = 0; c < nchan; c++) memcpy(&all[(size_t)c * ntaps], taps, (size_t)ntaps * sizeof(float));
-    install(d, all, ntaps);
-    *h = d;
-    return 0;
+    return op_created<drop<FakeRowFir>>(h, d, err);
 }
 int qdsp_hip_rowfir_set_taps(void* h, int chan, const float* taps, int ntaps) {
-    FakeRowFir* d = as_fir(h);
+    FakeRowFir* d = as<FakeRowFir>(h);
     if (!d || !taps || ntaps < 1 || ntaps > 4096 || (chan != -1 && (!chan_ok(d, chan) || ntaps != d->ntaps))) return QDSP_HIP_EINVAL;
     std::vector<float> all = d->taps;
     if (chan == -1) all.resize((size_t)d->nchan * ntaps);
@@ -162,94 +146,82 @@ int qdsp_hip_rowfir_set_taps(void* h, int chan, const float* taps, int ntaps) {
     return 0;
 }
 int qdsp_hip_rowfir_ntaps(void* h) {
-    FakeRowFir* d = as_fir(h);
+    FakeRowFir* d = as<FakeRowFir>(h);
     return d ? d->ntaps : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rowfir_get_history(void* h, int chan, float* hist) {
-    FakeRowFir* d = as_fir(h);
+    FakeRowFir* d = as<FakeRowFir>(h);
     if (!d || !chan_ok(d, chan) || !hist) return QDSP_HIP_EINVAL;
     const size_t row = (size_t)(d->ntaps - 1) * d->nc;
     if (row) memcpy(hist, &d->hist[chan * row], row * sizeof(float));
     return 0;
 }
 int qdsp_hip_rowfir_set_history(void* h, int chan, const float* hist) {
-    FakeRowFir* d = as_fir(h);
+    FakeRowFir* d = as<FakeRowFir>(h);
     if (!d || !chan_ok(d, chan) || !hist) return QDSP_HIP_EINVAL;
     const size_t row = (size_t)(d->ntaps - 1) * d->nc;
     if (row) memcpy(&d->hist[chan * row], hist, row * sizeof(float));
     return 0;
 }
 int qdsp_hip_rowfir_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    FakeRowFir* d = as_fir(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<FakeRowFir>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_rowfir_process(void* h, const float* in, int count, float* out) {
     return qdsp_hip_rowfir_process_ex(h, in, QDSP_HIP_LINK_HOST, count, out, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_rowfir_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                       void* hip_stream) {
-    FakeRowFir* d = as_fir(h);
-    return d ? (int)fir_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<FakeRowFir, fir_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_rowfir_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    return qdsp_hip_rowfir_process_batch_dev(h, d_in, count, count, d_out, count, hip_stream);
+    return op_process_dev<FakeRowFir, fir_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_rowfir_reset(void* h) {
-    FakeRowFir* d = as_fir(h);
+    FakeRowFir* d = as<FakeRowFir>(h);
     if (!d) return QDSP_HIP_EINVAL;
     d->hist.assign(d->hist.size(), 0.0f);
     return 0;
 }
-void qdsp_hip_rowfir_destroy(void* h) { drop(as_fir(h)); }
+void qdsp_hip_rowfir_destroy(void* h) { drop(as<FakeRowFir>(h)); }
 
 // ---- DelayImag ----
 int qdsp_hip_delay_imag_create(void** h, int device, int nchan, int max_block) {
-    if (h) *h = nullptr;
-    if (const int rc = stream_op_check(h, device, nchan, max_block)) return rc;
-    FakeDelay* d = new (std::nothrow) FakeDelay();
-    if (!d) return QDSP_HIP_ENOMEM;
-    d->launch = launch_as<FakeDelay, delay_launch>;
-    if (const hipError_t err = stream_op_init(d, device, nchan, max_block, 2 * sizeof(float), 2 * sizeof(float))) {
-        delete d;
-        return -(int)err;
-    }
+    FakeDelay* d = nullptr;
+    if (const int rc = op_new<FakeDelay, delay_launch>(&d, h, true, device, nchan, max_block)) return rc;
     d->last.assign((size_t)nchan, 0.0f);
-    *h = d;
-    return 0;
+    return op_created<drop<FakeDelay>>(h, d, stream_op_init(d, device, nchan, max_block, 2 * sizeof(float), 2 * sizeof(float)));
 }
 int qdsp_hip_delay_imag_get_state(void* h, int chan, float* last_im) {
-    FakeDelay* d = as_delay(h);
+    FakeDelay* d = as<FakeDelay>(h);
     if (!d || !chan_ok(d, chan) || !last_im) return QDSP_HIP_EINVAL;
     *last_im = d->last[chan];
     return 0;
 }
 int qdsp_hip_delay_imag_set_state(void* h, int chan, float last_im) {
-    FakeDelay* d = as_delay(h);
+    FakeDelay* d = as<FakeDelay>(h);
     if (!d || (chan != -1 && !chan_ok(d, chan))) return QDSP_HIP_EINVAL;
     for (int c = chan_first(chan), c1 = c + chan_count(d, chan); c < c1; c++) d->last[c] = last_im;
     return 0;
 }
 int qdsp_hip_delay_imag_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link) {
-    FakeDelay* d = as_delay(h);
-    return d ? (int)stream_op_process_ex(d, in, in_link, count, out, out_link) : QDSP_HIP_EINVAL;
+    return op_process_ex<FakeDelay>(h, in, in_link, count, out, out_link);
 }
 int qdsp_hip_delay_imag_process(void* h, const float* in_iq, int count, float* out_iq) {
     return qdsp_hip_delay_imag_process_ex(h, in_iq, QDSP_HIP_LINK_HOST, count, out_iq, QDSP_HIP_LINK_HOST);
 }
 int qdsp_hip_delay_imag_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride, void* d_out, int64_t out_stride,
                                           void* hip_stream) {
-    FakeDelay* d = as_delay(h);
-    return d ? (int)delay_launch(d, d_in, count, in_stride, d_out, out_stride, static_cast<hipStream_t>(hip_stream)) : QDSP_HIP_EINVAL;
+    return op_process_batch_dev<FakeDelay, delay_launch>(h, d_in, count, in_stride, d_out, out_stride, hip_stream);
 }
 int qdsp_hip_delay_imag_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream) {
-    return qdsp_hip_delay_imag_process_batch_dev(h, d_in, count, count, d_out, count, hip_stream);
+    return op_process_dev<FakeDelay, delay_launch>(h, d_in, count, d_out, hip_stream);
 }
 int qdsp_hip_delay_imag_reset(void* h) {
-    FakeDelay* d = as_delay(h);
+    FakeDelay* d = as<FakeDelay>(h);
     if (!d) return QDSP_HIP_EINVAL;
     d->last.assign(d->last.size(), 0.0f);
     return 0;
 }
-void qdsp_hip_delay_imag_destroy(void* h) { drop(as_delay(h)); }
+void qdsp_hip_delay_imag_destroy(void* h) { drop(as<FakeDelay>(h)); }
 
 }  // extern "C"

@@ -16,14 +16,16 @@ using namespace qh;
 namespace {
 
 struct FakeRs : StreamOp {
-    FakeRs() : StreamOp(0) {}
+    static constexpr OpKind kKind = OpKind::Rs;
     qrs::Params p;
     qrs::Field f;
     uint8_t in_map[256], out_map[256];
     std::vector<uint8_t> xr;
     int last_count = 0;
 };
-FakeRs* as_rs(void* h) { return static_cast<FakeRs*>(stream_op_registered(h, kKindRs)); }
+void drop(FakeRs* d) {
+    op_free(d, [] {});
+}
 
 uint8_t mul(const qrs::Field& f, uint8_t a, uint8_t b) { return (a && b) ? f.exp[f.log[a] + f.log[b]] : 0; }
 uint8_t dvd(const qrs::Field& f, uint8_t a, uint8_t b) { return (a && b) ? f.exp[255 + f.log[a] - f.log[b]] : 0; }     // x / 0 = 0
@@ -170,13 +172,7 @@ int qdsp_hip_rs_create(void** h, int device, int nchan, int max_block, int prim_
         d->launch = launch_as<FakeRs, launch>;
         rc = -(int)stream_op_init(d, device, nchan, max_block, (size_t)d->p.frame_in, (size_t)d->p.frame_out);
     }
-    if (rc) {
-        delete d;
-        return rc;
-    }
-    stream_op_register(d, kKindRs);
-    *h = d;
-    return 0;
+    return op_created<drop>(h, d, rc);
 }
 int qdsp_hip_falcon_rs_create(void** h, int device, int nchan, int max_block) {
     uint8_t to_db[256], from_db[256], rnd[255];
@@ -185,21 +181,21 @@ int qdsp_hip_falcon_rs_create(void** h, int device, int nchan, int max_block) {
     return qdsp_hip_rs_create(h, device, nchan, max_block, qrs::kCcsdsPoly, 120, 11, 16, 5, 4, 1, from_db, to_db, rnd, 255);
 }
 int qdsp_hip_rs_set_maps(void* h, const uint8_t* in_map, const uint8_t* out_map, const uint8_t* xor_seq, int xor_len) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     return (d && set_maps(d, in_map, out_map, xor_seq, xor_len)) ? 0 : QDSP_HIP_EINVAL;
 }
-int64_t qdsp_hip_rs_out_size(void* h, int64_t nframes) { return (as_rs(h) && nframes >= 0) ? nframes : QDSP_HIP_EINVAL; }
+int64_t qdsp_hip_rs_out_size(void* h, int64_t nframes) { return (as<FakeRs>(h) && nframes >= 0) ? nframes : QDSP_HIP_EINVAL; }
 int qdsp_hip_rs_frame_in_bytes(void* h) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     return d ? d->p.frame_in : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_frame_out_bytes(void* h) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     return d ? d->p.frame_out : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, int64_t in_stride_bytes, const int* d_in_counts, void* d_out,
                                   int64_t out_stride_bytes, int* d_counts, int* d_errs, void*) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     if (!d) return QDSP_HIP_EINVAL;
     const int64_t n = d_in_counts ? (d_in_counts[0] < 0 ? 0 : (d_in_counts[0] < nframes ? d_in_counts[0] : nframes)) : nframes;
     const int rc = launch_counts(d, d_in, nframes, in_stride_bytes, n, d_out, out_stride_bytes, d_errs);
@@ -207,17 +203,17 @@ int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, in
     return rc;
 }
 int qdsp_hip_rs_process_dev(void* h, const void* d_in, int64_t nframes, void* d_out, void* s) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     return d ? (int)launch(d, d_in, nframes, nframes, d_out, nframes, static_cast<hipStream_t>(s)) : QDSP_HIP_EINVAL;
 }
 int qdsp_hip_rs_get_counts(void* h, int* counts) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     if (!d || !counts) return QDSP_HIP_EINVAL;
     counts[0] = d->last_count;
     return 0;
 }
 int qdsp_hip_rs_process_ex(void* h, const void* in, int in_link, int nframes, void* out, int out_link) {
-    FakeRs* d = as_rs(h);
+    FakeRs* d = as<FakeRs>(h);
     if (!d || (out_link != QDSP_HIP_LINK_HOST && out_link != QDSP_HIP_LINK_DEVICE)) return QDSP_HIP_EINVAL;
     const int64_t rc = stream_op_process_ex(d, in, in_link, nframes, out, out_link);
     if (rc < 0 || nframes == 0) return (int)rc;
@@ -226,12 +222,6 @@ int qdsp_hip_rs_process_ex(void* h, const void* in, int in_link, int nframes, vo
 int qdsp_hip_rs_process(void* h, const uint8_t* in, int nframes, uint8_t* out) {
     return qdsp_hip_rs_process_ex(h, in, QDSP_HIP_LINK_HOST, nframes, out, QDSP_HIP_LINK_HOST);
 }
-void qdsp_hip_rs_destroy(void* h) {
-    FakeRs* d = as_rs(h);
-    if (!d) return;
-    stream_op_unregister(d);
-    stream_op_release(d);
-    delete d;
-}
+void qdsp_hip_rs_destroy(void* h) { drop(as<FakeRs>(h)); }
 
 }  // extern "C"

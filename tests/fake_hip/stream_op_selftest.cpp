@@ -8,6 +8,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 extern "C" int fake_hip_live(void);
@@ -25,7 +27,7 @@ constexpr int kMaxBlock = 64;
 constexpr size_t kInEs = 8, kOutEs = 4;
 
 struct Dummy : StreamOp {
-    Dummy() : StreamOp(kLevelMagic) {}
+    static constexpr OpKind kKind = OpKind::Level;
     int launches = 0;
     int64_t fail = 0;                      // what the next launches return instead of working
     const void* seen_in = nullptr;
@@ -51,22 +53,38 @@ int64_t dummy_launch(Dummy* d, const void* d_in, int64_t count, int64_t in_strid
 
 int64_t lag3(const StreamOp*, int64_t count) { return count > 3 ? count - 3 : 0; }
 
-Dummy* make(int nchan, int max_block, bool hook) {
-    void* h = nullptr;
-    if (stream_op_check(&h, 0, nchan, max_block)) return nullptr;
-    Dummy* d = new Dummy();
-    d->launch = launch_as<Dummy, dummy_launch>;
-    if (hook) d->out_count = lag3;
-    if (stream_op_init(d, 0, nchan, max_block, kInEs, kOutEs) != hipSuccess) {
-        delete d;
-        return nullptr;
-    }
-    return d;
+void drop(Dummy* d) {
+    op_free(d, [] {});
 }
 
-void drop(Dummy* d) {
-    stream_op_release(d);
-    delete d;
+// a create as the units write it: the shared head, the handle's own allocations, the shared tail
+Dummy* make(int nchan, int max_block, bool hook) {
+    void* h = &h;
+    Dummy* d = nullptr;
+    if (hook ? op_new<Dummy, dummy_launch, lag3>(&d, &h, true, 0, nchan, max_block) : op_new<Dummy, dummy_launch>(&d, &h, true, 0, nchan, max_block))
+        return nullptr;
+    if (h || op_created<drop>(&h, d, stream_op_init(d, 0, nchan, max_block, kInEs, kOutEs))) return nullptr;
+    return static_cast<Dummy*>(h);
+}
+
+// one more type per kind, so that as<Other> can be asked of every kind
+template <OpKind K>
+struct Of : StreamOp {
+    static constexpr OpKind kKind = K;
+};
+template <int K>
+bool kind_is_told_apart() {
+    Of<(OpKind)K> op;
+    constexpr int other = K == (int)kLastOpKind ? 1 : K + 1;
+    if (as_stream_op(&op) || as<Of<(OpKind)K>>(&op)) return false;                   // not registered: no handle
+    stream_op_register(&op, (OpKind)K);
+    const bool ok = as_stream_op(&op) == &op && as<Of<(OpKind)K>>(&op) == &op && !as<Of<(OpKind)other>>(&op);
+    stream_op_unregister(&op);
+    return ok && !as_stream_op(&op) && !as<Of<(OpKind)K>>(&op);
+}
+template <int... K>
+bool kinds_are_told_apart(std::integer_sequence<int, K...>) {
+    return (kind_is_told_apart<K + 1>() && ...);
 }
 
 int links() {
@@ -201,24 +219,45 @@ int creation() {
         Dummy* d = new Dummy();
         fake_hip_fail_malloc(nth);
         CHECK(stream_op_init(d, 0, 1, kMaxBlock, kInEs, kOutEs) != hipSuccess);
-        CHECK(fake_hip_live() == base && !d->stream && !d->ev0 && !d->ev1 && !d->d_in && !d->d_out && d->magic == 0 && !as_stream_op(d));
+        CHECK(fake_hip_live() == base && !d->stream && !d->ev0 && !d->ev1 && !d->d_in && !d->d_out && !as_stream_op(d));
         stream_op_release(d);                                                     // (what the operator's own free does next: harmless)
         CHECK(fake_hip_live() == base);
         delete d;
     }
     fake_hip_fail_malloc(0);
-    // as_stream_op: the seven kinds, and nothing else
-    for (uint32_t m : {kDemodMagic, kDeempMagic, kLevelMagic, kStereoFmMagic, kFfAgcMagic, kCagcMagic, kCostasMagic}) {
-        StreamOp op(m);
-        CHECK(as_stream_op(&op) == &op);
-    }
+    // the shared head of a create: the operator's own refusal first, then the shared checks; *h is nulled in every case
+    Dummy* none = nullptr;
+    h = &h;
+    CHECK((op_new<Dummy, dummy_launch>(&none, &h, false, 7, 1, 0)) == QDSP_HIP_EINVAL && !h && !none);
+    h = &h;
+    CHECK((op_new<Dummy, dummy_launch>(&none, &h, true, 7, 1, 0)) == QDSP_HIP_ENODEV && !h && !none);
+    CHECK((op_new<Dummy, dummy_launch>(&none, nullptr, true, 0, 1, 0)) == QDSP_HIP_EINVAL && !none);
+    // the shared tail: a failed create frees the handle, hands nothing out and never made it one
+    CHECK((op_new<Dummy, dummy_launch>(&none, &h, true, 0, 1, 0)) == 0 && none && !h && !as_stream_op(none));
+    CHECK(op_created<drop>(&h, none, hipErrorOutOfMemory) == -(int)hipErrorOutOfMemory && !h && !as_stream_op(none) && fake_hip_live() == base);
+    // every kind of the enum: taken by as_stream_op and by as<> of its own kind, refused by as<> of another; only while registered
+    CHECK(kinds_are_told_apart(std::make_integer_sequence<int, (int)kLastOpKind>()));
     struct Foreign { uint32_t magic; int pad[64]; } chan = {0x4348414eu, {0}}, engine = {0x51445350u, {0}}, math = {0x514d4154u, {0}};
     CHECK(!as_stream_op(nullptr) && !as_stream_op(&chan) && !as_stream_op(&engine) && !as_stream_op(&math));
+    // memory that begins with a magic of the earlier scheme ("QLVL", "QDMD"): refused
+    Foreign old_level = {0x514c564cu, {0}}, old_demod = {0x51444d44u, {0}};
+    CHECK(!as_stream_op(&old_level) && !as<Dummy>(&old_level) && !as_stream_op(&old_demod));
     Dummy* d = make(1, 4, false);
-    CHECK(d && as_stream_op(d) == static_cast<StreamOp*>(d) && d->in_es == kInEs && d->out_es == kOutEs && d->max_block == 4);
-    stream_op_release(d);
-    CHECK(!as_stream_op(d) && fake_hip_live() == base);                            // released: refused
-    delete d;
+    CHECK(d && as_stream_op(d) == static_cast<StreamOp*>(d) && as<Dummy>(d) == d && d->in_es == kInEs && d->out_es == kOutEs && d->max_block == 4);
+    // unregistered: refused, though the memory is still a StreamOp; a second unregister does nothing
+    stream_op_unregister(d);
+    CHECK(!as_stream_op(d) && !as<Dummy>(d));
+    stream_op_unregister(d);
+    CHECK(!as_stream_op(d));
+    stream_op_register(d, Dummy::kKind);
+    CHECK(as<Dummy>(d) == d);
+    // destroyed: the pointer is to freed memory, and the lookups refuse it without reading it (this build would report the read);
+    // a second destroy -- the unit's free of what as<> returns -- is a call with null
+    void* stale = d;
+    drop(d);
+    CHECK(!as_stream_op(stale) && !as<Dummy>(stale) && fake_hip_live() == base);
+    drop(as<Dummy>(stale));
+    CHECK(fake_hip_live() == base);
     return 0;
 }
 
@@ -237,7 +276,8 @@ int uploads() {
 }  // namespace
 
 int main() {
-    static_assert(offsetof(StreamOp, magic) == 0, "every as_* reads the magic at offset 0");
+    static_assert(std::is_standard_layout<StreamOp>::value && !std::is_polymorphic<Dummy>::value,
+                  "a handle is cast to the StreamOp it begins with and back (static_cast): no virtual functions, no second base");
     if (creation() || links() || output_count_hook() || timing() || uploads()) return 1;
     printf("stream_op ok\n");
     return 0;

@@ -345,8 +345,9 @@ def test_argument_errors(torch):
 
 
 def test_handles_are_known_by_kind_and_only_while_alive(torch):
-    """The two kinds carry no magic: a handle is looked up by address.  A handle of the other kind, of an older kind, a destroyed
-    one and plain memory are all QDSP_HIP_EINVAL, and the shared entry points (last_kernel) take the live ones."""
+    """Like every per-row kind, the two are looked up by address in the library's handle table.  A handle of the other kind, of
+    another unit's kind, a destroyed one and plain memory are all QDSP_HIP_EINVAL, and the shared entry points (last_kernel) take
+    the live ones.  (tests/test_gpu_handles.py asks the same of all fourteen kinds.)"""
     L_ = capi.load()
     sync = np.array([1, 0, 1, 1], np.uint8)
     d, t, fm = ops.Deframer(16, sync, 0, nchan=1, max_block=64), ops.Threshold(nchan=1, max_block=64), ops.AmDemod(nchan=1, max_block=64)

@@ -62,14 +62,24 @@ def test_ops_surface():
 
 
 def test_stream_op_takes_the_new_kinds():
+    """The kinds of RowFir, DelayImagOp and the chain exist in the one enum of handle kinds, their handles name them, and
+    as_stream_op takes every kind of the enum (it asks the table for the address alone); the fourteen kinds' values all differ."""
     hdr = open(os.path.join(CSRC, "stream_op.h")).read()
     src = open(os.path.join(CSRC, "stream_op.cpp")).read()
+    enum = re.search(r"enum class OpKind : int \{(.*?)\n\};", hdr, re.S).group(1)
+    entries = re.findall(r"^\s*(\w+)(?:\s*=\s*(\d+))?,", enum, re.M)
+    values, nxt = {}, 0
+    for name, explicit in entries:                      # the values as the compiler counts them
+        nxt = int(explicit) if explicit else nxt
+        values[name] = nxt
+        nxt += 1
+    for kind, where in (("RowFir", "rowfir.hip.h"), ("DelayImag", "rowfir.hip.h"), ("Chain", "psk_chain.cpp")):
+        assert kind in values, kind
+        assert f"static constexpr OpKind kKind = OpKind::{kind};" in open(os.path.join(CSRC, where)).read(), kind
     body = src[src.index("StreamOp* as_stream_op"):src.index("int stream_op_check")]
-    for magic in ("kRowFirMagic", "kDelayImagMagic", "kChainMagic"):
-        assert re.search(rf"constexpr uint32_t {magic} = 0x[0-9a-f]{{8}}u;", hdr), magic
-        assert magic in body, magic
-    values = re.findall(r"constexpr uint32_t k\w+Magic = (0x[0-9a-f]{8})u;", hdr)
-    assert len(values) == len(set(values)) == 11
+    assert "lookup(h" in body and "OpKind::" not in body and "->" not in body       # any kind, and h is not read
+    assert not re.search(r"k\w+Magic\s*=", hdr) and "magic" not in src
+    assert len(values) == len(set(values.values())) == 14 and 0 not in values.values()
 
 
 # ---- build ----

@@ -8,7 +8,8 @@ the test pool and not wanted).
 * qdsp_amd/csrc/ring.cpp: the halo ring's buffer rotation against a fake synchronous HIP runtime + one-rank RCCL under
   -fsanitize=address,undefined;
 * qdsp_amd/csrc/stream_op.cpp: the host path the per-row operators share (link codes, staging, error precedence, creation and
-  release) with a dummy operator on the same fake runtime, under -fsanitize=address,undefined.
+  release, the handle table by kind, stale and foreign addresses) with a dummy operator on the same fake runtime, under
+  -fsanitize=address,undefined; and the table's lookups against concurrent creates and destroys under -fsanitize=thread.
 * qdsp_amd/csrc/select.cpp: filter planning and kernel selection, recomputing every line of the recorded dispatch map
   (tests/golden/dispatch_map.txt) under -fsanitize=address,undefined -- any change of dispatch shows as a diff of that file.
 Pass = every program exits 0 and no sanitizer report appears on stderr."""
@@ -176,6 +177,21 @@ def test_stream_op_host_path_under_asan_ubsan():
     cxx(flags + ["-Wall", "-D__HIP_PLATFORM_AMD__", f"-I{hip_inc}", "-o", os.path.join(out, "stream_op_selftest"), "stream_op_selftest.cpp",
                  os.path.join(ROOT, "qdsp_amd", "csrc", "stream_op.cpp"), f"-L{out}", "-lfakehip", "-Wl,-rpath,$ORIGIN"])
     assert "stream_op ok" in run_clean([os.path.join(out, "stream_op_selftest")], cwd=out)
+
+
+def test_handle_table_lookups_against_create_and_destroy_under_tsan():
+    """The handle table of qdsp_amd/csrc/stream_op.cpp (lookups under a shared lock, register and unregister under the exclusive
+    one): threads that create, look up and destroy dummy handles against threads that look up foreign and just-destroyed addresses."""
+    hip_inc = "/opt/rocm/include"
+    if not os.path.exists(os.path.join(hip_inc, "hip", "hip_runtime.h")):
+        pytest.skip("needs the HIP headers")
+    out = os.path.join(FAKE, "build", "thread_stream_op")
+    os.makedirs(out, exist_ok=True)
+    flags = BASE + ["-fsanitize=thread"]
+    cxx(flags + ["-fPIC", "-shared", "-DFAKE_HIP", "-o", os.path.join(out, "libfakehip.so"), "fake_hip_runtime.cpp"])
+    cxx(flags + ["-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", f"-I{hip_inc}", "-o", os.path.join(out, "stream_op_race"), "stream_op_race.cpp",
+                 os.path.join(ROOT, "qdsp_amd", "csrc", "stream_op.cpp"), f"-L{out}", "-lfakehip", "-Wl,-rpath,$ORIGIN"])
+    assert "stream_op race ok" in run_clean([os.path.join(out, "stream_op_race")], cwd=out)
 
 
 def test_selector_recomputes_the_dispatch_map_under_asan_ubsan():
