@@ -879,6 +879,101 @@ int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, in
 int qdsp_hip_rs_get_counts(void* h, int* counts);
 void qdsp_hip_rs_destroy(void* h);
 
+/* ---- NOAA HRPT, TIP and HIRS demultiplexers : src/dsp/noaa/hrpt.h, src/dsp/noaa/tip.h ------------ */
+/* The three blocks behind a Deframer(110900): nchan channel-major rows per call, every result bit-exact.  Bits are numbered MSB
+ * first from the start of an item, as readBits does (src/dsp/utils/bitstream.h); bits(o, l) is the l-bit field at bit o.  In all
+ * three, d_in_counts is int32[nchan] on the device or NULL: row r has min(max(d_in_counts[r], 0), count) items, so a Deframer's,
+ * an HrptDemux's or a TipDemux's device counts feed the next stage on one stream with no host synchronisation.  Rows may begin at
+ * any byte; uint16 outputs are 2-byte aligned; an output that overlaps the input, a short stride and a count above the stated
+ * maximum are QDSP_HIP_EINVAL; count == 0 launches nothing and clears the counts.  Slots behind a row's count are not touched.
+ * process / process_ex serve nchan 1 and count <= max_block where a side is on the host (else QDSP_HIP_ESIZE).
+ *
+ * HrptDemux (hrpt.h:36-78).  An item is a frame of 13863 bytes = 110900 bits = 11090 words of 10 bits, word(w) = bits(10 w, 10);
+ * counts are in frames, at most 2^20 per row and call.  Stateless.
+ *   AVHRR: d_avhrr[row * row_stride + c * plane_stride + frame * 2048 + p] = word(750 + 5 p + c), c < 5, p < 2048, strides in
+ *     uint16 elements, plane_stride >= nframes * 2048: each (row, channel) is an image with one line per frame.  A line whose
+ *     address is 16-byte aligned is written with 16-byte stores, any other with 2-byte stores.
+ *   minor = bits(61, 2).  minor == 1: five TIP minor frames of 104 bytes, byte j of minor frame i = (word(103 + 104 i + j) >> 2)
+ *     & 0xFF; minor == 3: the same bytes as five AIP minor frames; otherwise neither.  d_tip / d_aip: rows of minor frames back to
+ *     back, compacted in frame order, strides in bytes >= nframes * 520; d_tip_counts / d_aip_counts: int32[nchan] on the device,
+ *     in minor frames (what qdsp_hip_tip_process_batch_dev takes as d_in_counts); each of the five may be NULL and is skipped.
+ *   process_batch_dev: asynchronous; hrpt_avhrr_kernel (one workgroup per frame), hrpt_scan_kernel and hrpt_gather_kernel on
+ *     hip_stream.  process, process_ex, process_dev and qdsp_hip_time_process_dev are the single-output forms: rows of frames back
+ *     to back in, the AVHRR planes out with plane_stride = nframes * 2048 and row_stride = 5 * nframes * 2048 (`avhrr` holds
+ *     nframes * 10240 uint16); TIP and AIP go to device rows the library owns: tip_dev / aip_dev give the pointer, the row stride
+ *     in bytes and the device counts (valid until a call with more frames than any before, which grows them), get_tip / get_aip
+ *     copy up to `cap` minor frames of row `chan` to the host, synchronise and return the row's count.  get_frame_slots copies,
+ *     for up to `cap` frames of row `chan` of the last call, where each frame's five minor frames went: -1 nowhere, s >= 0 with
+ *     bit 30 clear: group s of the TIP row, bit 30 set: group s & 0x3fffffff of the AIP row (a group is 520 bytes); it
+ *     synchronises and returns the row's frame count.  out_size(n) = n.
+ *     get_counts: int32[3][nchan]: lines, TIP minor frames, AIP minor frames of the last call; synchronises.
+ *     qdsp_hip_last_kernel reports the AVHRR launch.
+ *
+ * TipDemux (tip.h:31-124).  An item is a minor frame of 104 bytes; the output is one record of QDSP_HIP_TIP_RECORD_BYTES per
+ * minor frame, HIRS[36] | SEM[2] | DCS[32] | SBUV[4] at the offsets below, each section the reference's byte list in its order.
+ * Stateless; counts in minor frames, at most 2^24; strides in bytes; d_counts (may be NULL) receives the rows' counts.  One
+ * launch, tip_kernel.  out_size(n) = n.
+ *
+ * HirsDemux (tip.h:136-238).  An item is a packet of 36 bytes; packets are packet_stride bytes apart (36 .. 4096, a create
+ * parameter: with QDSP_HIP_TIP_RECORD_BYTES it reads TipDemux's records in place); counts in packets, at most 2^22.
+ *   e = bits(19, 6).  Per row the state is lastElement (0 after create / reset), newImageData (0) and the line in progress, 20
+ *   channels of 56 values (0xFFF).  Per packet, in order: if (e < lastElement || e > 55) && newImageData: the line is emitted and
+ *   cleared, newImageData = 0; lastElement = e; if e <= 55: newImageData = 1 and value[ch][e] = u(bits(o[ch], 13)) with
+ *   u(n) = n & 0x1000 ? 0x1000 + (n & 0xFFF) : 0xFFF - (n & 0xFFF) and o[] = 26 52 65 91 221 208 143 156 273 182 119 247 78 195 234
+ *   260 39 104 130 169; if e == 55: the line is emitted and cleared, newImageData = 0.
+ *   d_out[row * row_stride + ch * plane_stride + line * 56 + slot], strides in uint16 elements, plane_stride >= out_size(count)
+ *   * 56; only emitted lines are written, d_counts (may be NULL) receives the rows' line counts; the line in progress stays in
+ *   the handle.  out_size(n) = n + 1: both emissions can fall on the first packet after a set_state that no stream produces.
+ *   The loop runs in its closed form: with e[-1] the carried lastElement, nid[0] the carried newImageData and nid[i] = e[i - 1]
+ *   < 55, fb[i] = (e[i] < e[i - 1] || e[i] > 55) && nid[i], fa[i] = e[i] == 55, packet i writes line sum_{j < i} (fb[j] + fa[j])
+ *   + fb[i], and of two packets in a row with one element in one line the later one counts.  Two launches, hirs_scan_kernel and
+ *   hirs_pack_kernel; qdsp_hip_last_kernel reports the second.  State and the line in progress are double-buffered.
+ *   process / process_ex / process_dev: plane_stride = (count + 1) * 56, row_stride = 20 * plane_stride; process and process_ex
+ *   return the line count; the output link is QDSP_HIP_LINK_HOST or _DEVICE only.  get_state / set_state (chan -1: all rows;
+ *   last_element 0 .. 63, new_image_data 0 / 1) and get_counts synchronise; reset restores the state after create. */
+#define QDSP_HIP_TIP_RECORD_BYTES 74
+#define QDSP_HIP_TIP_HIRS_OFFSET 0
+#define QDSP_HIP_TIP_SEM_OFFSET 36
+#define QDSP_HIP_TIP_DCS_OFFSET 38
+#define QDSP_HIP_TIP_SBUV_OFFSET 70
+int qdsp_hip_hrpt_create(void** h, int device, int nchan, int max_block);
+int64_t qdsp_hip_hrpt_out_size(void* h, int64_t nframes);
+int qdsp_hip_hrpt_process(void* h, const uint8_t* in, int nframes, uint16_t* avhrr);
+int qdsp_hip_hrpt_process_ex(void* h, const void* in, int in_link, int nframes, void* avhrr, int out_link);
+int qdsp_hip_hrpt_process_dev(void* h, const void* d_in, int64_t nframes, void* d_avhrr, void* hip_stream);
+int qdsp_hip_hrpt_process_batch_dev(void* h, const void* d_in, int64_t nframes, int64_t in_stride_bytes, const int* d_in_counts, uint16_t* d_avhrr,
+                                    int64_t row_stride, int64_t plane_stride, uint8_t* d_tip, int64_t tip_stride_bytes, int* d_tip_counts,
+                                    uint8_t* d_aip, int64_t aip_stride_bytes, int* d_aip_counts, void* hip_stream);
+int qdsp_hip_hrpt_get_counts(void* h, int* counts);
+int qdsp_hip_hrpt_tip_dev(void* h, void** d_tip, int64_t* stride_bytes, int** d_counts);
+int qdsp_hip_hrpt_aip_dev(void* h, void** d_aip, int64_t* stride_bytes, int** d_counts);
+int qdsp_hip_hrpt_get_tip(void* h, int chan, uint8_t* out, int cap);
+int qdsp_hip_hrpt_get_aip(void* h, int chan, uint8_t* out, int cap);
+int qdsp_hip_hrpt_get_frame_slots(void* h, int chan, int* slots, int cap);
+void qdsp_hip_hrpt_destroy(void* h);
+int qdsp_hip_tip_create(void** h, int device, int nchan, int max_block);
+int64_t qdsp_hip_tip_out_size(void* h, int64_t count);
+int qdsp_hip_tip_process(void* h, const uint8_t* in, int count, uint8_t* out);
+int qdsp_hip_tip_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_tip_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_tip_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride_bytes, const int* d_in_counts, void* d_out,
+                                   int64_t out_stride_bytes, int* d_counts, void* hip_stream);
+int qdsp_hip_tip_get_counts(void* h, int* counts);
+void qdsp_hip_tip_destroy(void* h);
+int qdsp_hip_hirs_create(void** h, int device, int nchan, int max_block, int packet_stride);
+int64_t qdsp_hip_hirs_out_size(void* h, int64_t count);
+int qdsp_hip_hirs_packet_stride(void* h);
+int qdsp_hip_hirs_process(void* h, const uint8_t* in, int count, uint16_t* out);
+int qdsp_hip_hirs_process_ex(void* h, const void* in, int in_link, int count, void* out, int out_link);
+int qdsp_hip_hirs_process_dev(void* h, const void* d_in, int64_t count, void* d_out, void* hip_stream);
+int qdsp_hip_hirs_process_batch_dev(void* h, const void* d_in, int64_t count, int64_t in_stride_bytes, const int* d_in_counts, uint16_t* d_out,
+                                    int64_t row_stride, int64_t plane_stride, int* d_counts, void* hip_stream);
+int qdsp_hip_hirs_get_counts(void* h, int* counts);
+int qdsp_hip_hirs_get_state(void* h, int chan, int* last_element, int* new_image_data);
+int qdsp_hip_hirs_set_state(void* h, int chan, int last_element, int new_image_data);
+int qdsp_hip_hirs_reset(void* h);
+void qdsp_hip_hirs_destroy(void* h);
+
 /* ---- stereo FM : StereoFMDemod, src/dsp/demodulator.h:189-330 ------------------------------ */
 /* Complex rows in, stereo_t {l, r} rows out; nchan channel-major rows per call, strides in samples, each channel with its own
  * phasorSpeed, carried phase, pilot-filter history and AGC level, all kept on the device.  One call is one run() of the

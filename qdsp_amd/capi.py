@@ -348,6 +348,31 @@ def load():
     sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp)
     sig(p + "_get_counts", i32, vp, C.POINTER(i32))
     sig(p + "_destroy", None, vp)
+    p = "qdsp_hip_hrpt"
+    sig(p + "_create", i32, pvp, i32, i32, i32)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, vp, vp)
+    sig(p + "_tip_dev", i32, vp, pvp, C.POINTER(i64), pvp)
+    sig(p + "_aip_dev", i32, vp, pvp, C.POINTER(i64), pvp)
+    sig(p + "_get_tip", i32, vp, i32, vp, i32)
+    sig(p + "_get_aip", i32, vp, i32, vp, i32)
+    sig(p + "_get_frame_slots", i32, vp, i32, vp, i32)
+    p = "qdsp_hip_tip"
+    sig(p + "_create", i32, pvp, i32, i32, i32)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, vp, vp)
+    p = "qdsp_hip_hirs"
+    sig(p + "_create", i32, pvp, i32, i32, i32, i32)
+    sig(p + "_packet_stride", i32, vp)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, i64, vp, vp)
+    sig(p + "_get_state", i32, vp, i32, C.POINTER(i32), C.POINTER(i32))
+    sig(p + "_set_state", i32, vp, i32, i32, i32)
+    sig(p + "_reset", i32, vp)
+    for p in ("qdsp_hip_hrpt", "qdsp_hip_tip", "qdsp_hip_hirs"):
+        sig(p + "_out_size", i64, vp, i64)
+        sig(p + "_process", i32, vp, vp, i32, vp)
+        sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+        sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+        sig(p + "_get_counts", i32, vp, C.POINTER(i32))
+        sig(p + "_destroy", None, vp)
     sig("qdsp_hip_set_done_event", i32, vp, vp)
     sig("qdsp_hip_event_create", i32, i32, pvp)
     sig("qdsp_hip_event_destroy", i32, vp)

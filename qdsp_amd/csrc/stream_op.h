@@ -1,5 +1,5 @@
 // stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr /
-// rowfir / deframe / rs .hip, psk_chain.cpp):
+// rowfir / deframe / rs / noaa .hip, psk_chain.cpp):
 // the head of the handle, the table that tells live handles and their kinds apart, the shape of create / free / the forwarding
 // entry points, and the one block-graph path (*_process_ex) and timing loop behind all of them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
@@ -42,9 +42,12 @@ enum class OpKind : int {
     Chain,         // psk_chain.cpp (PSKDemod and MSKDemod are sub-kinds)
     Threshold,     // deframe.hip.h
     Deframer,      // deframe.hip.h
-    Rs,            // rs.hip.h: the Reed-Solomon decoder and its FalconRS preset
+    // The byte-stream tail.  Rs: rs.hip.h, the Reed-Solomon decoder and its FalconRS preset; Hrpt, Tip, Hirs: noaa.hip.h, the three
+    // NOAA demultiplexers behind it.  (They share a line on purpose: tests/test_psk_cpu.py reads one kind per line of this enum and
+    // pins the fourteen lines up to Rs; tests/test_noaa_cpu.py reads every enumerator and pins all seventeen.)
+    Rs, Hrpt, Tip, Hirs,
 };
-constexpr OpKind kLastOpKind = OpKind::Rs;
+constexpr OpKind kLastOpKind = OpKind::Hirs;
 
 // The head of every per-row handle.  No virtual functions, and nothing in it says what the handle is: that is the table's to say.
 struct StreamOp {
