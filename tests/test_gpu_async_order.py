@@ -24,10 +24,15 @@ device atomics and every kernel's arithmetic order is fixed), and the serial run
   * the forward error correction handles of qdsp_amd.fec (RsDecoder, FalconRs, and Deframer -> FalconRs through the deframer's
     device counts): _rs_ref.Layout.decode under the maps in force -- set_maps switches the model's layout --, bit for bit over the
     whole output buffer, the counts and the whole errs buffer, each filled with a sentinel by a copy queued in front of the call
-    (bytes behind a row's last good frame and errs entries behind a short row included); frames from test_gpu_rs.gen_frames.
+    (bytes behind a row's last good frame and errs entries behind a short row included); frames from test_gpu_rs.gen_frames;
+  * the NOAA HRPT tail of qdsp_amd.noaa (HrptDemux, TipDemux, HirsDemux, and Deframer -> HrptDemux -> TipDemux -> HirsDemux through
+    the device counts): the definition of tests/_noaa_ref.py (hrpt_demux_fast, tip_demux, one HirsFast per row carried through the
+    steps: set_state and reset change it as they change the handle), bit for bit over whole sentinel-filled output allocations
+    and every getter's value (counts, get_state, tip, aip, qdsp_hip_hrpt_get_frame_slots); every row's HIRS elements climb from
+    call to call, so that a line in progress spans every host action.
 
 `test_control_*` proves that the hold holds and that a race shows; `test_scenarios_cover_the_library` (last) that every kernel
-family and every public setter / getter / reset / configure of qdsp_amd.ops and qdsp_amd.fec was raced.  With ASYNC_ORDER_REPORT=<file> the measured
+family and every public setter / getter / reset / configure of qdsp_amd.ops, qdsp_amd.fec and qdsp_amd.noaa was raced.  With ASYNC_ORDER_REPORT=<file> the measured
 host times and the holds used go there (profiles/async_order_windows.txt is one such run)."""
 import ctypes as C
 import inspect
@@ -42,6 +47,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _async as A  # noqa: E402
 import _deframer_ref as DF  # noqa: E402
 import _mmcr_ref as MM  # noqa: E402
+import _noaa_ref as NR  # noqa: E402
 import _numerics as NU  # noqa: E402
 import _rs_ref as RS  # noqa: E402
 import oracle as O  # noqa: E402
@@ -72,7 +78,8 @@ _SEEN = set()                      # kernel names of the async runs
 _RACED = set()                     # (class name, method) of every host action that ran with its window open
 PER_ROW_FAMILIES = {"fm_demod_kernel", "am_sub_kernel", "ssb_demod_kernel", "deemp_row_kernel", "deemp_scan_kernel", "level_row_kernel",
                     "level_apply_kernel", "stereo_mix_kernel", "ff_agc_kernel", "cagc_row_kernel", "cagc_scan_kernel", "costas_kernel",
-                    "mm_clock_kernel", "row_fir_kernel", "delay_imag_kernel", "threshold_kernel", "deframe_match_kernel", "rs_decode_kernel"}
+                    "mm_clock_kernel", "row_fir_kernel", "delay_imag_kernel", "threshold_kernel", "deframe_match_kernel", "rs_decode_kernel",
+                    "hrpt_avhrr_kernel", "tip_kernel", "hirs_pack_kernel"}
 DMA = {"fir_fft_dma_kernel", "fir_fft_dmapk_kernel"}     # members of the 4096-point overlap-save family (conftest.kname)
 OVERLAP_SAVE = DMA | {"fir_fft_kernel", "fir_fft1k_kernel", "pfb_dec8_kernel", "pfb_dec4_kernel", "pfb_dec8_real_kernel", "pfb_dec4_real_kernel"}
 DIRECT_FORMS = {"fir_core_kernel", "fir_lat_kernel", "decim_win_kernel", "decim_mfma_kernel", "decim_mfma_real_kernel", "resamp_lm_kernel",
@@ -1816,6 +1823,477 @@ def test_deframer_to_falcon_rs_count_handover(ops, fec):
     assert 0 < good < taken, (good, taken)
 
 
+# ------------------------------------------------------------------------------------------------ the NOAA HRPT tail (qdsp_amd.noaa)
+NOAA_S16, NOAA_S8 = 0xA5C3, 0x5A               # sentinels: no AVHRR or HIRS value (> 0x1FFF), and a byte
+
+
+@pytest.fixture(scope="module")
+def noaa(ops):
+    from qdsp_amd import noaa as _noaa
+
+    return _noaa
+
+
+def _fresh(shape, value, dtype):
+    """A function that gives a new device tensor filled with the sentinel `value` by a copy queued on the current stream."""
+    import torch
+
+    src = _dev(np.full(shape, value, dtype))
+
+    def fresh():
+        out = torch.empty_like(src)
+        out.copy_(src)
+        return out
+
+    return fresh
+
+
+def _eff(in_counts, n, rows):
+    return [n] * rows if in_counts is None else [min(max(int(c), 0), n) for c in in_counts]
+
+
+def _is(v, want, what):
+    assert np.array_equal(np.asarray(v), np.asarray(want)), f"{what}: {v} / the model's {want}"
+
+
+class _HirsModel:
+    """One _noaa_ref.HirsFast per row, carried through the steps as the handle carries its state and its line in progress."""
+
+    def __init__(self, rows, stride):
+        self.refs, self.stride, self.last_counts = [NR.HirsFast() for _ in range(rows)], stride, np.zeros(rows, np.int32)
+
+    def set_state(self, last_element, new_image_data, chan=-1):
+        for r in (range(len(self.refs)) if chan < 0 else [chan]):
+            self.refs[r].set_state(last_element, new_image_data)
+
+    def reset(self):
+        for ref in self.refs:
+            ref.reset()
+
+    def get_state(self, chan):
+        return self.refs[chan].last_element, self.refs[chan].new_image_data
+
+    def lines(self, x, eff):
+        out = [ref.process(x[r][:eff[r] * self.stride], self.stride) for r, ref in enumerate(self.refs)]
+        self.last_counts = np.asarray([ln.shape[1] for ln in out], np.int32)
+        return out
+
+    def check(self, got, x, eff, label):
+        """got: the whole output allocation (sentinel-filled in front of the call) and the counts."""
+        out, counts = got
+        want = np.full_like(out, NOAA_S16)
+        for r, ln in enumerate(self.lines(x, eff)):
+            want[r, :, :ln.shape[1]] = ln
+        assert counts.tolist() == self.last_counts.tolist(), f"{label}: counts {counts.tolist()} / the definition's {self.last_counts.tolist()}"
+        assert A.same_bits(out, want), f"{label}: output allocation: {np.argwhere(out != want)[:4].tolist()}"
+
+
+def _hirs_call(label, op, model, x, n, in_counts=None):
+    """op.process_batch over the rows x (rows, n * packet_stride bytes; row stride + 1) into a sentinel-filled allocation with one
+    line of slack, per-row counts from a device tensor that is itself copied on the current stream."""
+    rows = len(x)
+    xin, fresh = _In(x, rows=True), _fresh((rows, 20, n + 2, 56), NOAA_S16, np.uint16)
+    cin = None if in_counts is None else _In(np.asarray(in_counts, np.int32))
+
+    def fn():
+        out = fresh()
+        _, counts = op.process_batch(xin(), out[:, :, :n + 1], count=n, in_counts=None if cin is None else cin())
+        return out, counts
+
+    return _checked(Call(label, fn, op, {"hirs_pack_kernel"}), lambda v: model.check(v, x, _eff(in_counts, n, rows), label))
+
+
+def _state_is(model, chan):
+    return lambda v: _is((int(v[0]), bool(v[1])), model.get_state(chan), f"get_state({chan})")
+
+
+@pytest.mark.parametrize("rows,stride", [(ROWS, 36), (ROWS_WAVE, 74)])
+def test_noaa_hirs(ops, noaa, rows, stride):
+    """HirsDemux: get_state, set_state for all rows and for one, counts, reset, a count == 0 call and a call longer than any before
+    (hirs_scratch frees and reallocates the map while the call before it is queued), each with a call still held.  Every row's
+    elements climb by one from call to call, so a line in progress spans every action: set_state(60 .., True) makes the next
+    packet flush it, reset drops it, and a setter that wrote the state buffers early would be overwritten by the held calls.
+    Runs of two and of three calls in front of the actions: both of the double-buffered state slots are the current one."""
+    from test_gpu_noaa import Climb
+
+    def scenario():
+        op = noaa.HirsDemux(packet_stride=stride, nchan=rows, max_block=8)
+        model, gen = _HirsModel(rows, stride), Climb(rows, 360, stride)
+        steps = []
+
+        def call(n, in_counts=None):
+            eff = _eff(in_counts, n, rows)
+            x = np.stack([gen.packets(r, n, eff[r]) for r in range(rows)])
+            steps.append(_hirs_call(f"process_batch {len(steps)} ({n})", op, model, x, n, in_counts))
+
+        def host(method, *args, act=None, check=None):
+            steps.append(_checked(H(op, method, *args), (lambda v: act()) if act else check))
+
+        def same_counts(v):
+            _is(v[0], model.last_counts, "counts")
+
+        mixed = [(6, 0, 9, -1, 3)[r % 5] for r in range(rows)]
+        call(6), call(6)
+        host("get_state", 2, check=_state_is(model, 2))
+        call(6), call(6), call(6)
+        host("set_state", 60, True, act=lambda: model.set_state(60, True))
+        call(6), call(6)
+        host("set_state", 62, True, 3, act=lambda: model.set_state(62, True, 3))
+        call(6), call(6, mixed)
+        host("counts", check=same_counts)
+        call(6), call(0, mixed)
+        host("counts", check=same_counts)
+        call(6), call(6), call(6)
+        host("reset", act=model.reset)
+        call(6), call(6)
+        host("get_state", rows - 1, check=_state_is(model, rows - 1))
+        call(6), call(40), call(40)                   # longer than any call before
+        host("counts", check=same_counts)
+        call(6), call(6, mixed), call(6)
+        host("set_state", 61, True, rows - 2, act=lambda: model.set_state(61, True, rows - 2))
+        call(6), call(6)
+        host("get_state", rows - 2, check=_state_is(model, rows - 2))
+        return steps
+
+    serial = _three_ways(f"noaa hirs {rows} rows", scenario)
+    _anchor(serial)
+    lines = sum(int(v[1].sum()) for (_, v), st in zip(serial.outputs, serial.steps) if st.label.startswith("process_batch"))
+    assert lines >= 3 * rows                              # the setters' flushes, and the lines that end by themselves
+
+
+def test_noaa_hirs_one_row(ops, noaa):
+    """HirsDemux with one row: the 1-D tensor form (launch on the caller's stream, then its own download of the line count: it
+    drains the queue, so a process_batch call on a (1, n) view goes in front of each and behind it; the first is longer than
+    max_block), get_state and counts."""
+    from test_gpu_noaa import Climb
+
+    def scenario():
+        op = noaa.HirsDemux(nchan=1, max_block=8)
+        model, gen = _HirsModel(1, 36), Climb(1, 361, 36)
+        steps = []
+
+        def batch(n):
+            steps.append(_hirs_call(f"process_batch {len(steps)} ({n})", op, model, gen.packets(0, n)[None, :], n))
+
+        def one_d(n):
+            x = gen.packets(0, n)
+            xin, label = _In(x), f"process {len(steps)} ({n})"
+            steps.append(_checked(Call(label, lambda: op.process(xin()), op, {"hirs_pack_kernel"}),
+                                  lambda v: A.same_bits(v[0], model.lines([x], [n])[0]) or pytest.fail(f"{label}: not the definition's lines")))
+
+        batch(6)
+        one_d(45)
+        batch(6)
+        one_d(7)
+        batch(6)
+        steps.append(_checked(H(op, "get_state", 0), _state_is(model, 0)))
+        batch(6), batch(6)
+        steps.append(_checked(H(op, "counts"), lambda v: _is(v[0], model.last_counts, "counts")))
+        batch(6)
+        return steps
+
+    _anchor(_three_ways("noaa hirs one row", scenario))
+
+
+def _hrpt_frames(rng, rows, n):
+    """(rows, n, 13863) random bytes, the `minor` values 1, 3, 0, 1, 2, 3, 1 in turn, each row from another place in the cycle."""
+    fr = rng.integers(0, 256, (rows, n, NR.FRAME_BYTES)).astype(np.uint8)
+    for r in range(rows):
+        m = np.array([(1, 3, 0, 1, 2, 3, 1)[(f + 2 * r) % 7] for f in range(n)], np.uint8)
+        fr[r, :, 7] = (fr[r, :, 7] & 0xF9) | (m << 1)
+    return fr
+
+
+def _slot_ranks(minors):
+    want = np.full(len(minors), -1, np.int32)
+    want[minors == 1] = np.arange((minors == 1).sum())
+    want[minors == 3] = np.arange((minors == 3).sum()) | (1 << 30)
+    return want
+
+
+class _HrptModel:
+    """_noaa_ref.hrpt_demux_fast per row and call (no state between frames); what the getters report is the last call's."""
+
+    def __init__(self, rows):
+        self.rows, self.last_counts, self.minors, self.tip, self.aip = rows, np.zeros((3, rows), np.int32), [np.zeros(0, np.int64)] * rows, None, None
+
+    def run(self, fr, eff):
+        res = [NR.hrpt_demux_fast(fr[r, :eff[r]]) for r in range(self.rows)]
+        self.last_counts = np.asarray([eff, [len(q[1]) for q in res], [len(q[2]) for q in res]], np.int32)
+        self.minors, self.tip, self.aip = [q[3] for q in res], [q[1] for q in res], [q[2] for q in res]
+        return res
+
+    def check(self, got, fr, eff, label):
+        av, tip, tc, aip, ac = got
+        w_av, w_tip, w_aip = np.full_like(av, NOAA_S16), np.full_like(tip, NOAA_S8), np.full_like(aip, NOAA_S8)
+        for r, (a, t, p, _) in enumerate(self.run(fr, eff)):
+            w_av[r, :, :eff[r]] = a
+            w_tip[r, :t.size], w_aip[r, :p.size] = t.ravel(), p.ravel()
+        assert tc.tolist() == self.last_counts[1].tolist() and ac.tolist() == self.last_counts[2].tolist(), f"{label}: TIP / AIP counts"
+        for name, g, w in (("avhrr", av, w_av), ("tip", tip, w_tip), ("aip", aip, w_aip)):
+            assert A.same_bits(g, w), f"{label}: {name} allocation: {np.argwhere(g != w)[:4].tolist()}"
+
+
+def _frame_slots(op, chan, cap):
+    from qdsp_amd import capi
+
+    L = capi.load()
+
+    def fn():
+        buf = np.full(cap, -7, np.int32)
+        return np.int32(capi.check(L.qdsp_hip_hrpt_get_frame_slots(op._h, chan, buf.ctypes.data, cap))), buf
+
+    return Host(f"HrptDemux.get_frame_slots({chan})", fn, op, "get_frame_slots")
+
+
+def _slots_are(model, chan, cap):
+    def chk(v):
+        want = _slot_ranks(model.minors[chan])
+        m = min(len(want), cap)
+        assert int(v[0]) == len(want) and np.array_equal(v[1][:m], want[:m]) and (v[1][m:] == -7).all(), ("get_frame_slots", chan, v, want)
+    return chk
+
+
+def test_noaa_hrpt(ops, noaa):
+    """HrptDemux over 5 rows, process_batch into sentinel-filled torch-owned outputs: counts, qdsp_hip_hrpt_get_frame_slots, an
+    nframes == 0 call, per-row device counts, and a 5-frame call on a handle made for 2 (hrpt_scratch frees the slots and the
+    library's own TIP / AIP rows while the call before it is queued; that call's outputs are checked after the growth, like
+    every other), each host action with a call still held; own_dev at the end (host only: the stride of the grown rows)."""
+    rng = np.random.default_rng(44)
+
+    def scenario():
+        op = noaa.HrptDemux(nchan=ROWS, max_block=2)
+        model, steps = _HrptModel(ROWS), []
+
+        def call(n, in_counts=None):
+            fr, m, label = _hrpt_frames(rng, ROWS, n), max(n, 1), f"process_batch {len(steps)} ({n})"
+            xin, cin = _In(fr.reshape(ROWS, n * NR.FRAME_BYTES), rows=True), None if in_counts is None else _In(np.asarray(in_counts, np.int32))
+            fa, ft = _fresh((ROWS, 5, m + 1, 2048), NOAA_S16, np.uint16), _fresh((ROWS, m * 520 + 7), NOAA_S8, np.uint8)
+
+            def fn():
+                a, t, p = fa(), ft(), ft()
+                _, _, tc, _, ac = op.process_batch(xin(), nframes=n, in_counts=None if cin is None else cin(), avhrr=a[:, :, :m], tip=t, aip=p)
+                return a, t, tc, p, ac
+
+            steps.append(_checked(Call(label, fn, op, {"hrpt_avhrr_kernel"}), lambda v: model.check(v, fr, _eff(in_counts, n, ROWS), label)))
+
+        def same_counts(v):
+            _is(v[0], model.last_counts, "counts")
+
+        call(2), call(2)
+        steps.append(_checked(H(op, "counts"), same_counts))
+        call(2), call(2, [2, 0, 5, -1, 1])
+        steps.append(_checked(_frame_slots(op, 2, 4), _slots_are(model, 2, 4)))
+        call(2), call(0)
+        steps.append(_checked(H(op, "counts"), same_counts))
+        call(2), call(5), call(5)                     # more frames than any call before
+        steps.append(_checked(_frame_slots(op, 4, 3), _slots_are(model, 4, 3)))
+        call(3), call(3, [3, 1, 0, 3, 2])
+        steps.append(_checked(H(op, "counts"), same_counts))
+        call(2)
+        steps.append(_checked(Host("HrptDemux.own_dev", lambda: np.int64(op.own_dev("tip")[1]), op, "own_dev"), lambda v: _is(v[0], 5 * 520, "own_dev stride")))
+        return steps
+
+    rng_state = rng.bit_generator.state
+
+    def same_every_run():
+        rng.bit_generator.state = rng_state           # (every run of the scenario sees the same frames)
+        return scenario()
+
+    _anchor(_three_ways("noaa hrpt", same_every_run))
+
+
+def test_noaa_hrpt_one_row(ops, noaa):
+    """HrptDemux's single-output entry point (qdsp_hip_hrpt_process_dev: AVHRR to the caller, TIP and AIP into the library's own
+    rows) with tip(chan), aip(chan), get_frame_slots and counts as racing getters, and a 4-frame call on a handle made for 2: the
+    rows the getters read are freed and reallocated with the call before still queued."""
+    import torch
+
+    from qdsp_amd import capi
+
+    rng = np.random.default_rng(45)
+    frames = {k: _hrpt_frames(rng, 1, n) for k, n in enumerate([2, 2, 2, 2, 2, 2, 2, 4, 4, 3, 3])}
+
+    def scenario():
+        op = noaa.HrptDemux(nchan=1, max_block=2)
+        model, steps = _HrptModel(1), []
+
+        def single():
+            fr = frames[sum(not s.racing for s in steps)]
+            n = fr.shape[1]
+            xin, fresh, label = _In(fr.ravel()), _fresh(5 * n * 2048 + 16, NOAA_S16, np.uint16), f"process_dev {len(steps)} ({n})"
+
+            def fn():
+                out = fresh()
+                capi.check(int(op._fn("process_dev")(op._h, xin().data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)))
+                return out
+
+            def chk(v):
+                av = model.run(fr, [n])[0][0]
+                assert A.same_bits(v[0][:av.size], av.ravel()) and (v[0][av.size:] == NOAA_S16).all(), f"{label}: AVHRR lines"
+            steps.append(_checked(Call(label, fn, op, {"hrpt_avhrr_kernel"}), chk))
+
+        single(), single()
+        steps.append(_checked(H(op, "tip", 0), lambda v: A.same_bits(v[0], model.tip[0]) or pytest.fail("tip(0)")))
+        single(), single()
+        steps.append(_checked(H(op, "aip", 0), lambda v: A.same_bits(v[0], model.aip[0]) or pytest.fail("aip(0)")))
+        single(), single()
+        steps.append(_checked(_frame_slots(op, 0, 8), _slots_are(model, 0, 8)))
+        single(), single(), single()                  # 2, 4 and 4 frames
+        steps.append(_checked(H(op, "tip", 0), lambda v: A.same_bits(v[0], model.tip[0]) or pytest.fail("tip(0) after the growth")))
+        single(), single()
+        steps.append(_checked(H(op, "counts"), lambda v: _is(v[0], model.last_counts, "counts")))
+        return steps
+
+    serial = _three_ways("noaa hrpt one row", scenario)
+    _anchor(serial)
+    got = [v[0] for (_, v), st in zip(serial.outputs, serial.steps) if st.racing and (".tip" in st.label or ".aip" in st.label)]
+    assert len(got) == 3 and all(len(g) for g in got), "a getter that read no minor frame checked nothing"
+
+
+def test_noaa_tip(ops, noaa):
+    """TipDemux over 5 rows: counts, a count == 0 call, per-row device counts and a call longer than any before (two workgroups a
+    row), each getter with a call still held."""
+    rng = np.random.default_rng(46)
+    blocks = [rng.integers(0, 256, (ROWS, n, 104)).astype(np.uint8) for n in (5, 5, 5, 0, 5, 70, 70, 5)]
+    counts_of = {2: [5, 0, 9, -2, 3], 6: [70, 64, 65, 0, 1]}
+
+    def scenario():
+        op = noaa.TipDemux(nchan=ROWS, max_block=5)
+        steps, last = [], {}
+
+        def call():
+            k = sum(not s.racing for s in steps)
+            mf, in_counts = blocks[k], counts_of.get(k)
+            n = mf.shape[1]
+            eff, label = _eff(in_counts, n, ROWS), f"process_batch {len(steps)} ({n})"
+            xin, cin, fresh = _In(mf.reshape(ROWS, n * 104), rows=True), None if in_counts is None else _In(np.asarray(in_counts, np.int32)), _fresh((ROWS, n * 74 + 7), NOAA_S8, np.uint8)
+
+            def fn():
+                out = fresh()
+                _, counts = op.process_batch(xin(), out, count=n, in_counts=None if cin is None else cin())
+                return out, counts
+
+            def chk(v):
+                want = np.full_like(v[0], NOAA_S8)
+                for r in range(ROWS):
+                    want[r, :eff[r] * 74] = NR.tip_demux(mf[r, :eff[r]]).ravel()
+                last["counts"] = eff
+                assert v[1].tolist() == eff and A.same_bits(v[0], want), f"{label}: not the definition's records, or written past a row's count"
+            steps.append(_checked(Call(label, fn, op, {"tip_kernel"}), chk))
+
+        def counts():
+            steps.append(_checked(H(op, "counts"), lambda v: _is(v[0], last["counts"], "counts")))
+
+        call(), call()
+        counts()
+        call(), call()                                # device counts, then count == 0
+        counts()
+        call(), call(), call()                        # 5, then 70 twice: longer than any call before
+        counts()
+        call()
+        return steps
+
+    _anchor(_three_ways("noaa tip", scenario))
+
+
+def test_noaa_chain_with_a_racing_setter_and_growth(ops, noaa):
+    """Deframer(110900, the 60-bit sync) -> HrptDemux -> TipDemux -> HirsDemux(stride 74) over 2 rows, every stage reading the one
+    before's device counts, three rounds on one stream: HirsDemux.set_state(60, True) races the first round's held calls (the
+    next round's first packet then ends every row's line); the third round has 4 frames a row on an HrptDemux made for 2, so
+    hrpt_scratch frees the slots with the second round's kernels still queued.  A fresh Deframer per round (a round's bits end
+    inside the noise behind its last frame).  Reference: the rows' own frames, then the definition chain with one HirsFast per
+    row carried over the rounds."""
+    import torch
+
+    from test_noaa_cpu import noaa_check_input
+
+    frames, _ = noaa_check_input(9, min_lines=1)       # minors 1, 1, 3, 0, 1, 2, 1, 3, 1
+    rounds = [[frames[0:1], frames[6:7]], [frames[1:2], frames[8:9]], [frames[2:5], frames[[5, 7]]]]
+    sync = NR.sync_bits()
+
+    def round_bits(rows):
+        nf = max(len(fr) for fr in rows)
+        width = 41 + nf * NR.FRAME_BITS + 100
+        bits = np.zeros((2, width), np.uint8)
+        for r, fr in enumerate(rows):
+            b = np.unpackbits(fr, axis=1)[:, :NR.FRAME_BITS].ravel()
+            bits[r, 41 - 4 * r:41 - 4 * r + b.size] = b
+        return bits, np.array([width, 37 + len(rows[1]) * NR.FRAME_BITS + 80], np.int32)
+
+    inputs = [round_bits(rows) for rows in rounds]
+
+    def scenario():
+        hr, tp, hi = noaa.HrptDemux(nchan=2, max_block=2), noaa.TipDemux(nchan=2, max_block=20), noaa.HirsDemux(74, nchan=2, max_block=20)
+        model, steps = _HirsModel(2, 74), []
+
+        def one_round(k):
+            bits, nbits = inputs[k]
+            width = bits.shape[1]
+            df = ops.Deframer(NR.FRAME_BITS, sync, nchan=2, max_block=width)
+            cap = df.out_size(width)
+            x, xn, s = _In(bits), _In(nbits), {}
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.uint8, device="cuda")              # noqa: E731
+            zeros16 = lambda *shape: zeros(*shape[:-1], 2 * shape[-1]).view(torch.uint16)              # noqa: E731
+
+            def deframe():
+                s["frames"], s["nf"] = df.process_batch(x(), out=zeros(2, cap * NR.FRAME_BYTES), in_counts=xn())
+                return s["frames"], s["nf"]
+
+            def hrpt():
+                s["hr"] = hr.process_batch(s["frames"], nframes=cap, in_counts=s["nf"], avhrr=zeros16(2, 5, cap, 2048),
+                                           tip=zeros(2, cap * 520), aip=zeros(2, cap * 520))
+                return s["hr"]
+
+            def tip():
+                s["rec"], s["nr"] = tp.process_batch(s["hr"][1], zeros(2, 5 * cap * 74), count=5 * cap, in_counts=s["hr"][2])
+                return s["rec"], s["nr"]
+
+            def hirs():
+                return hi.process_batch(s["rec"], zeros16(2, 20, 5 * cap + 1, 56), count=5 * cap, in_counts=s["nr"])
+
+            ref = {}
+
+            def chk_deframe(v):
+                for r, fr in enumerate(rounds[k]):
+                    assert int(v[1][r]) == len(fr) and np.array_equal(v[0][r, :fr.size], fr.ravel()) and not v[0][r, fr.size:].any(), ("deframer", k, r)
+
+            def chk_hrpt(v):
+                a, t, tc, p, pc = v
+                ref["hr"] = [NR.hrpt_demux_fast(fr) for fr in rounds[k]]
+                for r, (av, tip_, aip_, _) in enumerate(ref["hr"]):
+                    nf = av.shape[1]
+                    assert np.array_equal(a[r][:, :nf], av) and not a[r][:, nf:].any() and int(tc[r]) == len(tip_) and int(pc[r]) == len(aip_), ("hrpt", k, r)
+                    assert np.array_equal(t[r, :tip_.size], tip_.ravel()) and not t[r, tip_.size:].any(), ("tip rows", k, r)
+                    assert np.array_equal(p[r, :aip_.size], aip_.ravel()) and not p[r, aip_.size:].any(), ("aip rows", k, r)
+
+            def chk_tip(v):
+                ref["rec"] = [NR.tip_demux(q[1]) for q in ref["hr"]]
+                for r, rec in enumerate(ref["rec"]):
+                    assert int(v[1][r]) == len(rec) and np.array_equal(v[0][r, :rec.size], rec.ravel()) and not v[0][r, rec.size:].any(), ("tip", k, r)
+
+            def chk_hirs(v):
+                x_rows = [rec.ravel() for rec in ref["rec"]]
+                for r, ln in enumerate(model.lines(x_rows, [len(rec) for rec in ref["rec"]])):
+                    assert int(v[1][r]) == ln.shape[1] and np.array_equal(v[0][r][:, :ln.shape[1]], ln) and not v[0][r][:, ln.shape[1]:].any(), ("hirs", k, r)
+
+            steps.extend([_checked(Call(f"deframe {k}", deframe, df), chk_deframe), _checked(Call(f"hrpt {k}", hrpt, hr, {"hrpt_avhrr_kernel"}), chk_hrpt),
+                          _checked(Call(f"tip {k}", tip, tp, {"tip_kernel"}), chk_tip), _checked(Call(f"hirs {k}", hirs, hi, {"hirs_pack_kernel"}), chk_hirs)])
+
+        one_round(0)
+        steps.append(_checked(H(hi, "set_state", 60, True), lambda v: model.set_state(60, True)))
+        one_round(1)
+        one_round(2)
+        steps.append(_checked(H(hi, "counts"), lambda v: _is(v[0], model.last_counts, "hirs counts")))
+        return steps
+
+    serial = _three_ways("noaa chain", scenario)
+    _anchor(serial)
+    out = dict(serial.outputs)
+    assert all(int(c) >= 1 for c in out["hirs 1"][1]), "set_state(60, True) ends every row's line in progress at the next packet"
+    assert sum(int(out[f"hrpt {k}"][2].sum() + out[f"hrpt {k}"][4].sum()) for k in range(3)) >= 25 and int(out["hirs 0"][1].sum()) >= 1
+
+
 # ------------------------------------------------------------------------------------------------ Math, Xlator alone, the sine source
 def test_math_xlator_and_sine_source(ops):
     from qdsp_amd import capi
@@ -1895,12 +2373,55 @@ def test_math_xlator_and_sine_source(ops):
 
 
 # ------------------------------------------------------------------------------------------------ release
-@pytest.mark.parametrize("which", ["engine", "per_row", "chain", "fec"])
+def _close_noaa():
+    """HirsDemux (its destroy frees the most: both state and partial-line slots, the map, the pinned count), HrptDemux (the slots
+    and its own TIP / AIP rows) and TipDemux, each closed behind two held calls into sentinel-filled torch-owned outputs."""
+    from qdsp_amd import noaa
+    from test_gpu_noaa import Climb
+
+    rng, gen, steps = np.random.default_rng(32), Climb(ROWS, 362, 36), []
+    hi, hr, tp = noaa.HirsDemux(nchan=ROWS, max_block=12), noaa.HrptDemux(nchan=ROWS, max_block=2), noaa.TipDemux(nchan=ROWS, max_block=9)
+    hmodel, rmodel = _HirsModel(ROWS, 36), _HrptModel(ROWS)
+    for k in range(2):
+        x = np.stack([gen.packets(r, 12) for r in range(ROWS)])
+        steps.append(_hirs_call(f"hirs {k}", hi, hmodel, x, 12))
+    steps.append(H(hi, "close"))
+    for k in range(2):
+        fr = _hrpt_frames(rng, ROWS, 2)
+        xin, fa, ft = _In(fr.reshape(ROWS, -1), rows=True), _fresh((ROWS, 5, 3, 2048), NOAA_S16, np.uint16), _fresh((ROWS, 2 * 520 + 7), NOAA_S8, np.uint8)
+
+        def fn(xin=xin, fa=fa, ft=ft):
+            a, t, p = fa(), ft(), ft()
+            _, _, tc, _, ac = hr.process_batch(xin(), nframes=2, avhrr=a[:, :, :2], tip=t, aip=p)
+            return a, t, tc, p, ac
+        steps.append(_checked(Call(f"hrpt {k}", fn, hr), lambda v, fr=fr, k=k: rmodel.check(v, fr, [2] * ROWS, f"hrpt {k}")))
+    steps.append(H(hr, "close"))
+    for k in range(2):
+        mf = rng.integers(0, 256, (ROWS, 9, 104)).astype(np.uint8)
+        xin, fresh = _In(mf.reshape(ROWS, -1), rows=True), _fresh((ROWS, 9 * 74 + 7), NOAA_S8, np.uint8)
+
+        def fn(xin=xin, fresh=fresh):
+            out = fresh()
+            return out, tp.process_batch(xin(), out, count=9)[1]
+
+        def chk(v, mf=mf):
+            want = np.full_like(v[0], NOAA_S8)
+            want[:, :9 * 74] = np.stack([NR.tip_demux(mf[r]).ravel() for r in range(ROWS)])
+            assert v[1].tolist() == [9] * ROWS and A.same_bits(v[0], want), "tip records behind a close"
+        steps.append(_checked(Call(f"tip {k}", fn, tp), chk))
+    steps.append(H(tp, "close"))
+    return steps
+
+
+@pytest.mark.parametrize("which", ["engine", "per_row", "chain", "fec", "noaa"])
 def test_close_while_the_last_call_is_held(ops, monkeypatch, which):
     """process into a torch-owned output, then close() while that call is still queued: every *_destroy waits for the device
-    before its first hipFree (Engine destroy, level_free, chain_free and the stages' own, rs_free), so the output is the serial
-    run's."""
+    before its first hipFree (Engine destroy, level_free, chain_free and the stages' own, rs_free, hirs_free / hrpt_free /
+    tip_free), so the output is the serial run's (and, for the NOAA handles, the definition's)."""
     _pin(monkeypatch, {})
+    if which == "noaa":
+        _anchor(_three_ways("close noaa", _close_noaa))
+        return
 
     def scenario():
         import torch
@@ -1941,23 +2462,30 @@ NOT_RACED = {
     ("Threshold", "reset"): "Threshold has no state: the method does nothing",
     ("RsDecoder", "reset"): "no state between frames: the method does nothing",
     ("FalconRs", "reset"): "no state between frames: the method does nothing",
+    ("HrptDemux", "reset"): "no state between frames: the method does nothing",
+    ("TipDemux", "reset"): "no state between minor frames: the method does nothing",
 }
+# getters of qdsp_amd.noaa that the name filter below does not find: raced all the same
+NOAA_GETTERS = {("HirsDemux", "counts"), ("HrptDemux", "counts"), ("HrptDemux", "tip"), ("HrptDemux", "aip"), ("HrptDemux", "get_frame_slots"),
+                ("TipDemux", "counts")}
 
 
 def test_scenarios_cover_the_library(ops):
     """Every kernel family of tests/test_gpu_fuzz.py's FAMILIES and every per-row kernel family ran in an async scenario, and every
-    public setter, getter, reset and configure of every operator class of qdsp_amd.ops and qdsp_amd.fec was a racing host action
-    (or is excluded above, with a reason)."""
-    from qdsp_amd import fec
+    public setter, getter, reset and configure of every operator class of qdsp_amd.ops, qdsp_amd.fec and qdsp_amd.noaa was a
+    racing host action (or is excluded above, with a reason)."""
+    from qdsp_amd import fec, noaa
 
     seen = set(_SEEN)
     if seen & DMA:
         seen.add("fir_fft_dma_kernel")
     missing = (FAMILIES | PER_ROW_FAMILIES) - seen
     assert not missing, f"kernel families no async scenario ran: {sorted(missing)} (seen: {sorted(seen)})"
+    assert NOAA_GETTERS <= _RACED, f"never a racing host action: {sorted(NOAA_GETTERS - _RACED)}"
     unraced, public, raced_methods = [], set(), set()
-    classes = [(n, c, m) for m in (ops, fec) for n, c in inspect.getmembers(m, inspect.isclass)]
+    classes = [(n, c, m) for m in (ops, fec, noaa) for n, c in inspect.getmembers(m, inspect.isclass)]
     assert {"RsDecoder", "FalconRs"} <= {n for n, c, m in classes if c.__module__ == fec.__name__}
+    assert {"HrptDemux", "TipDemux", "HirsDemux"} <= {n for n, c, m in classes if c.__module__ == noaa.__name__}
     for name, cls, mod in classes:
         if cls.__module__ != mod.__name__ or name.startswith("_"):
             continue

@@ -1,7 +1,10 @@
 """HrptDemux, TipDemux and HirsDemux on the GPU against the definition (tests/_noaa_ref.py), bit for bit, with sentinels around
 every output: row alignments and strides (both store forms of every kernel), per-row device counts, null outputs, calls cut at
 every position, state, the handle plumbing, the three operators behind a Deframer on one non-blocking stream, and the C++
-mirror's harness on the real library."""
+mirror's harness on the real library; the HRPT slot ranks past one wave and one pass of the scan, the HIRS state and line in
+progress through zero-count rows, count == 0 calls, set_state on one row of many and scans of several passes.  The conditions
+those inputs have to meet are asserted on the CPU when the module is imported (the *_plan functions and
+assert_minors_reach_every_rank_term)."""
 import ctypes as C
 import os
 
@@ -67,11 +70,75 @@ def hrpt_rows(nchan, n):
     return _FRAMES[nchan, n]
 
 
-def check_hrpt(torch, nchan, n, in_off, aligned, counts=None, skip=()):
+SCAN_WAVE, SCAN_PASS = 64, 256    # hrpt_scan_kernel: lanes of a wave (one ballot), frames of a pass (kHrptScanNT)
+LONG_N = [63, 64, 65, 255, 256, 257, 515]      # next to a wave, next to a pass, the pass-to-pass carry taken twice
+P_TIP, P_AIP = [0.45, 0.15, 0.3, 0.35, 0.2], [0.15, 0.45, 0.3, 0.1, 0.35]     # per row (mod 5): unequal, so the waves' totals differ
+
+
+def hrpt_long_minors(nchan, n, seed=7):
+    """(nchan, n) `minor` values drawn at random, every row with its own probabilities; the first two frames of every wave of the
+    first pass and of every later pass are a TIP and an AIP frame (which one first alternates with the row), so that every such
+    span holds both even where it is cut short behind its first frame."""
+    rng = np.random.default_rng(seed)
+    m = np.empty((nchan, n), np.uint8)
+    for r in range(nchan):
+        pt, pa = P_TIP[r % 5], P_AIP[r % 5]
+        m[r] = rng.choice(4, n, p=[(1 - pt - pa) * 0.5, pt, (1 - pt - pa) * 0.5, pa])
+        for s in scan_spans(n):
+            m[r, s[0]:s[0] + 2] = ([1, 3] if r % 2 == 0 else [3, 1])[:s[1] - s[0]]
+    return m
+
+
+def scan_spans(n):
+    """[first, end) of every wave of hrpt_scan_kernel's first pass and of every later pass, for a row of n frames."""
+    first = [(s, min(s + SCAN_WAVE, n)) for s in range(0, min(n, SCAN_PASS), SCAN_WAVE)]
+    return first + [(s, min(s + SCAN_PASS, n)) for s in range(SCAN_PASS, n, SCAN_PASS)]
+
+
+def assert_minors_reach_every_rank_term(m, n):
+    """The inputs' own conditions, on the CPU: in the first n frames every wave of the first pass and every pass holds a TIP and an
+    AIP frame in every row (a span of one frame: a TIP frame in one row and an AIP frame in another), and the waves' totals differ
+    -- equal totals could hide a wave offset taken from the wrong wave."""
+    m = m[:, :n]
+    for a, b in scan_spans(n):
+        if b - a >= 2:
+            assert all((m[r, a:b] == v).any() for r in range(len(m)) for v in (1, 3)), (n, a, b)
+        else:
+            assert {1, 3} <= set(m[:, a].tolist()), (n, a)
+    if n > SCAN_WAVE:
+        for r in range(len(m)):
+            for v in (1, 3):
+                totals = [int((m[r, a:b] == v).sum()) for a, b in scan_spans(min(n, SCAN_PASS))]
+                assert len(set(totals)) >= 2, (n, r, v, totals)
+
+
+LONG_MINORS = hrpt_long_minors(2, max(LONG_N))             # the sizes of LONG_N are its prefixes
+COUNTS_MINORS = hrpt_long_minors(5, 257, seed=8)
+for _n in LONG_N:
+    assert_minors_reach_every_rank_term(LONG_MINORS, _n)
+for _n in (257, 65):                                       # the per-row device counts of test_hrpt_device_counts_past_one_pass
+    assert_minors_reach_every_rank_term(COUNTS_MINORS, _n)
+
+
+def hrpt_long_rows(minors, n):
+    """(frames (nchan, n, 13863) of random bytes with minors[:, :n] in the `minor` field, the definition's results per row);
+    computed once per (minors, n)."""
+    key = (id(minors), n)
+    if key not in _FRAMES:
+        nchan = len(minors)
+        fr = np.random.default_rng(1000 + n).integers(0, 256, (nchan, n, R.FRAME_BYTES), dtype=np.uint8)
+        fr[:, :, 7] = (fr[:, :, 7] & 0xF9) | (minors[:, :n] << 1)
+        ref = [R.hrpt_demux_fast(fr[r]) for r in range(nchan)]
+        assert all(np.array_equal(ref[r][3], minors[r, :n]) for r in range(nchan))
+        _FRAMES[key] = fr, ref
+    return _FRAMES[key]
+
+
+def check_hrpt(torch, nchan, n, in_off, aligned, counts=None, skip=(), data=None):
     """One process_batch call on rows that begin `in_off` bytes into an allocation; `aligned`: strides and bases that allow the
     16-byte (AVHRR) and 4-byte (TIP / AIP) stores, else odd ones.  Everything the call may write is compared with the definition,
-    everything else with the sentinels."""
-    fr, ref = hrpt_rows(nchan, n)
+    everything else with the sentinels.  `data`: (frames, the definition's results) in place of hrpt_rows(nchan, n)."""
+    fr, ref = hrpt_rows(nchan, n) if data is None else data
     m = max(n, 1)
     x = dev_rows(torch, [fr[r].ravel() for r in range(nchan)], n * R.FRAME_BYTES + (0 if aligned else 5), in_off)
     ps = m * 2048 + (8 if aligned else 3)
@@ -102,7 +169,8 @@ def check_hrpt(torch, nchan, n, in_off, aligned, counts=None, skip=()):
         wt.append(len(tip))
         wa.append(len(aip))
     for name, d, want, base in (("avhrr", av_d, want_av, av_host), ("tip", tip_d, want_tip, tip_host), ("aip", aip_d, want_aip, aip_host)):
-        assert np.array_equal(d.cpu().numpy(), base if name in skip else want), (name, nchan, n, in_off, aligned, counts, skip)
+        got_h, want_h = d.cpu().numpy(), base if name in skip else want
+        assert np.array_equal(got_h, want_h), (name, nchan, n, in_off, aligned, counts, skip, "first at", np.flatnonzero(got_h != want_h)[:4].tolist())
     if "tip_counts" not in skip:
         assert got[2].cpu().numpy().tolist() == wt
     if "aip_counts" not in skip:
@@ -158,6 +226,48 @@ def test_hrpt_single_output_forms_and_cuts(torch):
     ptr, stride, cnt = op.own_dev("tip")
     assert ptr and cnt and stride >= 3 * 520
     assert op.out_size(5) == 5
+    op.close()
+
+
+@pytest.mark.parametrize("n", LONG_N)
+def test_hrpt_scan_past_one_wave_and_one_pass(torch, n):
+    """hrpt_scan_kernel's three rank terms -- the ballot below the lane, the totals of the waves below (through LDS) and the
+    totals carried from pass to pass -- on two rows of random `minor` sequences (assert_minors_reach_every_rank_term): a wrong
+    term puts two frames into one TIP / AIP slot and leaves another slot's sentinels, with the counts still right.  Both store
+    forms; the AVHRR lines too, but for the longest size."""
+    data = hrpt_long_rows(LONG_MINORS, n)
+    for aligned in (True, False):
+        wt, wa = check_hrpt(torch, 2, n, 8 if aligned else 3, aligned, skip=("avhrr",) if n > 257 else (), data=data)
+        assert wt == [5 * int((LONG_MINORS[r, :n] == 1).sum()) for r in range(2)] and min(wt) > 0 and min(wa) > 0
+
+
+@pytest.mark.parametrize("aligned", [True, False])
+def test_hrpt_device_counts_past_one_pass(torch, aligned):
+    """One call of 257 frames over five rows whose device counts are 257, 0, 65, 300 and -1: the scan's loop ends per row, the
+    gather's grid is the call's."""
+    check_hrpt(torch, 5, 257, 5 if aligned else 8, aligned, counts=[257, 0, 65, 300, -1], data=hrpt_long_rows(COUNTS_MINORS, 257))
+
+
+def test_hrpt_frame_slots_past_one_pass(torch):
+    """qdsp_hip_hrpt_get_frame_slots after a single-row call of 257 frames: TIP frame k -> k, AIP frame k -> k | 1 << 30, any
+    other -1, from the definition's `minor` values; the frame count is returned, min(count, cap) entries are written."""
+    n = 257
+    fr, ref = hrpt_long_rows(LONG_MINORS, n)
+    av, tip, aip, minors = ref[0]
+    want = np.full(n, -1, np.int32)
+    want[minors == 1] = np.arange((minors == 1).sum())
+    want[minors == 3] = np.arange((minors == 3).sum()) | (1 << 30)
+    assert (want[SCAN_PASS:] >= 0).any() and (want[SCAN_WAVE:SCAN_PASS] >= 0).any() and sorted(set(want.tolist()))[0] == -1
+    op = noaa.HrptDemux(max_block=n)
+    a, t, p = op.process(dev(torch, fr[0].ravel()))
+    assert np.array_equal(a.cpu().numpy(), av) and np.array_equal(t, tip) and np.array_equal(p, aip)
+    L = capi.load()
+    for cap in (100, n, 300):
+        slots = np.full(cap + 3, -7, np.int32)
+        assert L.qdsp_hip_hrpt_get_frame_slots(op._h, 0, slots.ctypes.data, cap) == n
+        m = min(n, cap)
+        assert np.array_equal(slots[:m], want[:m]) and (slots[m:] == -7).all(), cap
+    assert L.qdsp_hip_hrpt_get_frame_slots(op._h, 0, None, 0) == n and L.qdsp_hip_hrpt_get_frame_slots(op._h, 1, slots.ctypes.data, 1) == EINVAL
     op.close()
 
 
@@ -232,8 +342,9 @@ def spread(pk, stride, rng):
     return out.ravel()
 
 
-def check_hirs(torch, op, rows, n, stride, off, aligned, refs, counts=None):
-    """One process_batch call of `n` packets per row on `op`; refs: one HirsFast per row, carried along like the handle's state."""
+def check_hirs(torch, op, rows, n, stride, off, aligned, refs, counts=None, lines_out=None, states=False):
+    """One process_batch call of `n` packets per row on `op`; refs: one HirsFast per row, carried along like the handle's state.
+    `lines_out`: a list that takes the definition's lines of every row; `states`: get_state of every row is compared too."""
     nchan = len(rows)
     x = dev_rows(torch, rows, max(len(r) for r in rows) + (0 if aligned else 3), off)
     ps = (n + 1) * 56 + (8 if aligned else 5)
@@ -250,8 +361,14 @@ def check_hirs(torch, op, rows, n, stride, off, aligned, refs, counts=None):
         lines = refs[r].process(rows[r][:c * stride], stride)
         strided(want, (nchan, 20, n + 1, 56), (rs, ps, 56, 1), o_off)[r, :, :lines.shape[1]] = lines
         wc.append(lines.shape[1])
-    assert np.array_equal(out_d.cpu().numpy(), want), (nchan, n, stride, off, aligned, counts)
+        if lines_out is not None:
+            lines_out.append(lines)
+    got = out_d.cpu().numpy()
+    assert np.array_equal(got, want), (nchan, n, stride, off, aligned, counts, np.flatnonzero(got != want)[:4].tolist())
     assert cnt.cpu().numpy().tolist() == wc and op.counts().tolist() == wc
+    if states:
+        got_st = [op.get_state(r) for r in range(nchan)]
+        assert got_st == [(ref.last_element, ref.new_image_data) for ref in refs], (n, counts, got_st)
     return wc
 
 
@@ -271,6 +388,158 @@ def test_hirs_rows(torch, nchan, stride):
         for r in (0, nchan - 1):
             assert op.get_state(r) == (refs[r].last_element, refs[r].new_image_data)
     assert total >= 3 * nchan and op.last_kernel()["name"] == "hirs_pack_kernel"
+    op.close()
+
+
+CARRY_ROWS, CARRY_STRIDE = 17, 74
+
+
+class Climb:
+    """Per row, packets whose elements go up by one from where the row's last ones ended (55 ends the line, 0 follows it)."""
+
+    def __init__(self, nchan, seed, stride=CARRY_STRIDE):
+        self.rng, self.pos, self.stride = np.random.default_rng(seed), [(3 * r) % 40 for r in range(nchan)], stride
+
+    def packets(self, r, n, eff=None, kind="climb"):
+        """n packets of row r of which the first `eff` are the row's: the others carry element 55, which would end a line if a
+        kernel read past the row's count."""
+        eff = n if eff is None else eff
+        pk = hirs_packets(self.rng, n, "random") if kind == "random" else self.rng.integers(0, 256, (n, 36)).astype(np.uint8)
+        for i in range(n):
+            if i >= eff:
+                R._put_bits(pk[i], R.ELEMENT_BIT, R.ELEMENT_LEN, 55)
+            elif kind == "climb":
+                R._put_bits(pk[i], R.ELEMENT_BIT, R.ELEMENT_LEN, self.pos[r])
+                self.pos[r] = 0 if self.pos[r] == 55 else self.pos[r] + 1
+        return spread(pk, self.stride, self.rng)
+
+
+def hirs_carry_plan():
+    """The calls of test_hirs_lines_carried_through_every_kind_of_call -- (count, per-row device counts, the rows' bytes) -- and, from
+    the definition alone, the proof that they hold what the test is for.  Rows 0, 3, .. 15 ("idle") have a line in progress after
+    call 0, get count 0 in calls 1 and 2 (one flip of the state and partial-line buffers each way) while the other rows get
+    packets; call 2 has negative counts and counts above the call's; call 3 has count == 0 for all (no flip); call 4 ends every
+    row's line."""
+    nchan, eff = CARRY_ROWS, lambda c, n: min(max(c, 0), n)
+    spec = [(12, [12 - r % 5 for r in range(nchan)]),
+            (9, [0 if r % 3 == 0 else 9 - r % 4 for r in range(nchan)]),
+            (7, [0 if r % 3 == 0 else (-1 - r if r % 3 == 1 else 7 + r) for r in range(nchan)]),
+            (0, [3] * nchan),
+            (75, [75 - r for r in range(nchan)]),
+            (30, [(35, -3, 0, 17)[r % 4] for r in range(nchan)]),
+            (5, [5] * nchan)]
+    gen, calls = Climb(nchan, 330), []
+    for k, (n, counts) in enumerate(spec):
+        kind = lambda r: "random" if k == 5 and r % 2 else "climb"      # noqa: E731
+        calls.append((n, counts, [gen.packets(r, n, eff(counts[r], n), kind(r)) for r in range(nchan)]))
+    # the definition's run
+    refs, idle = [R.HirsFast() for _ in range(nchan)], list(range(0, nchan, 3))
+    snap, spans = {}, 0
+    for k, (n, counts, rows) in enumerate(calls):
+        if k == 3:
+            before = [(ref.buf.copy(), ref.new_image_data) for ref in refs]
+        lines = [refs[r].process(rows[r][:eff(counts[r], n) * CARRY_STRIDE], CARRY_STRIDE) for r in range(nchan)]
+        if k == 0:
+            for r in idle:
+                snap[r] = refs[r].buf.copy()
+                assert refs[r].new_image_data and 0 < (snap[r] != 0xFFF).any(axis=0).sum() < 55, r
+        if k in (1, 2):
+            assert all(eff(counts[r], n) == 0 and np.array_equal(refs[r].buf, snap[r]) for r in idle)
+            assert sum(eff(counts[r], n) > 0 for r in range(nchan)) >= 5
+        if k == 2:
+            assert min(counts) < 0 and max(counts) > n
+        if k == 4:
+            shared = 0
+            for r in range(nchan):
+                buf, nid = before[r]
+                w = buf != 0xFFF
+                assert lines[r].shape[1] >= 1 and np.array_equal(lines[r][:, 0][w], buf[w]), r
+                shared += bool(nid and w.any())
+            assert shared >= 12                      # rows whose line is shared by the calls before and after call 3
+            for r in idle:
+                w = snap[r] != 0xFFF
+                spans += bool(np.array_equal(lines[r][:, 0][w], snap[r][w]) and (lines[r][:, 0][~w] != 0xFFF).any())
+    assert spans >= 3 and len(calls) >= 6
+    return calls
+
+
+HIRS_CARRY = hirs_carry_plan()
+
+
+def test_hirs_lines_carried_through_every_kind_of_call(torch):
+    """17 rows, every call with per-row device counts (hirs_carry_plan): a line in progress survives two calls in which its row has
+    no packet while others have (hirs_scan_kernel's n == 0 branch and hirs_pack_kernel's line == total == 0 path, once per
+    buffer) and a call with count == 0; after every call the whole output allocation, the counts and every row's state are the
+    definition's."""
+    op = noaa.HirsDemux(packet_stride=CARRY_STRIDE, nchan=CARRY_ROWS, max_block=80)
+    refs = [R.HirsFast() for _ in range(CARRY_ROWS)]
+    emitted = 0
+    for k, (n, counts, rows) in enumerate(HIRS_CARRY):
+        emitted += sum(check_hirs(torch, op, rows, n, CARRY_STRIDE, (5 * k + 1) % 16, k % 2 == 0, refs, counts, states=True))
+    assert emitted >= CARRY_ROWS
+    op.close()
+
+
+def hirs_long_plan():
+    """(count, the two rows' bytes) of test_hirs_scan_past_one_pass; in every row a line ends (element 55) in every span of 256
+    packets that is at least 100 long, so that every pass hands a running total on and takes one."""
+    rng, calls = np.random.default_rng(340), []
+    for n, kinds in [(511, ("lines", "lines")), (512, ("lines", "random")), (513, ("lines", "lines")), (777, ("random", "lines"))]:
+        rows = [spread(hirs_packets(rng, n, kind), 36, rng) for kind in kinds]
+        for row in rows:
+            e = R.hirs_fields_fast(row)[0]
+            assert all((e[s:s + 256] == 55).any() for s in range(0, n - 100, 256)), (n, kinds)
+        calls.append((n, rows))
+    return calls
+
+
+HIRS_LONG = hirs_long_plan()
+
+
+def test_hirs_scan_past_one_pass(torch):
+    """Calls of 511, 512, 513 and 777 packets on one handle of two rows: hirs_scan_kernel's running line number is carried over one,
+    two and three passes of 256 packets, with lines ending in every pass."""
+    op = noaa.HirsDemux(nchan=2, max_block=777)
+    refs = [R.HirsFast(), R.HirsFast()]
+    for k, (n, rows) in enumerate(HIRS_LONG):
+        wc = check_hirs(torch, op, rows, n, 36, (3 * k + 2) % 16, k % 2 == 1, refs, states=True)
+        assert min(wc) >= 3
+    op.close()
+
+
+def test_hirs_set_state_on_one_row_of_many(torch):
+    """set_state(.., chan=5) with lines in progress on all 17 rows: row 5 follows the definition's set_state, the others go on with
+    their lines; set_state for all rows; reset clears every row's line in progress."""
+    nchan = CARRY_ROWS
+    gen = Climb(nchan, 350)
+    op = noaa.HirsDemux(packet_stride=CARRY_STRIDE, nchan=nchan, max_block=16)
+    refs = [R.HirsFast() for _ in range(nchan)]
+
+    def call(k, n):
+        lines = []
+        check_hirs(torch, op, [gen.packets(r, n) for r in range(nchan)], n, CARRY_STRIDE, 3 * k + 1, k % 2 == 0, refs, states=True, lines_out=lines)
+        return lines
+
+    assert all(ln.shape[1] == 0 for ln in call(0, 10)) and all(ref.new_image_data and (ref.buf != 0xFFF).any() for ref in refs)
+    carried = [ref.buf.copy() for ref in refs]
+    op.set_state(60, True, chan=5)
+    refs[5].set_state(60, True)
+    lines = call(1, 6)
+    assert [ln.shape[1] for ln in lines] == [int(r == 5) for r in range(nchan)]       # row 5 alone flushes: its element fell below 60
+    assert np.array_equal(lines[5][:, 0], carried[5])
+    assert all(((ref.buf == c) | (c == 0xFFF)).all() for r, (ref, c) in enumerate(zip(refs, carried)) if r != 5)   # the others' lines go on
+    op.set_state(7, False, chan=-1)
+    for ref in refs:
+        ref.set_state(7, False)
+    call(2, 8)
+    assert any(ref.new_image_data and (ref.buf != 0xFFF).any() for ref in refs)
+    op.reset()
+    for ref in refs:
+        ref.reset()
+    assert all(op.get_state(r) == (0, False) for r in range(nchan))
+    gen.pos = [55] * nchan
+    lines = call(3, 1)
+    assert all(ln.shape[1] == 1 and (ln[:, 0, :55] == 0xFFF).all() and (ln[:, 0, 55] != 0xFFF).any() for ln in lines)
     op.close()
 
 
