@@ -879,6 +879,79 @@ int qdsp_hip_rs_process_batch_dev(void* h, const void* d_in, int64_t nframes, in
 int qdsp_hip_rs_get_counts(void* h, int* counts);
 void qdsp_hip_rs_destroy(void* h);
 
+/* ---- FalconPacketSync : src/dsp/falcon_packet.h --------------------------------------------------- */
+/* The last block of the Falcon 9 chain, behind FalconRS: nchan channel-major rows of frames per call, every result bit-exact.
+ * An item is a frame; frames are frame_stride bytes apart (1195 .. 4096, a create parameter: with 1275 it reads the FalconRS
+ * output in place); every count on the input side is in FRAMES.  Of a frame only bytes 0 .. 1194 are read: b0 .. b3, then
+ * data[0 .. 1191).
+ *   pkt = b3 | (b2 & 7) << 8 (11 bits), ctr = (b2 >> 3) | b1 << 5 | (b0 & 0x3f) << 13 (19 bits).
+ * Per row the state is lastCounter (uint32, 0 after create / reset), packetRead (-1 after create / reset, otherwise 1 .. 16392)
+ * and the packetRead pending bytes.  Per frame, in order:
+ *   1. if uint32(lastCounter + 1) != ctr the pending packet is dropped (packetRead = -1); then lastCounter = ctr.  (The counter
+ *      has 19 bits and the comparison 32: the wrap from 2^19 - 1 to 0 counts as a missed frame, as in the reference.)
+ *   2. pkt == 2047, a continuation frame: if a packet is pending all 1191 data bytes are appended; nothing is emitted.
+ *   3. otherwise, if a packet is pending, data[0 .. pkt) is appended and the pending packet is emitted with packetRead + pkt bytes
+ *      (its own length field is not consulted); packetRead = -1.
+ *   4. then (in every frame that is no continuation frame) the walk from i = pkt while i < 1191: if 1191 - i < 4 the bytes
+ *      [i, 1191) become the pending packet and the walk ends; len = ((data[i] & 15) << 8 | data[i + 1]) + 2; len <= 2 ends the
+ *      walk with nothing pending; if 1191 - i < len, [i, 1191) becomes the pending packet and the walk ends; otherwise
+ *      data[i .. i + len) is emitted and i += len.
+ *   Two departures, both where the reference reads or writes past a buffer.  Overflow: a pending packet never passes the
+ *   reference's 0x4008 = 16392 bytes; an append that would pass it, in step 2 or 3, drops the pending packet instead (the
+ *   reference writes past packet[]).  Bad pointer: a pkt of 1192 .. 2046 lies outside the data area; the pending packet is
+ *   dropped, nothing is emitted and nothing becomes pending (the reference copies pkt bytes from a 1191-byte area).
+ *   The reference's printf and its unused pktId read are not reproduced.
+ * Output: the emitted packets of a row go back to back into the row's output bytes, in emission order; d_offs[row * offs_stride +
+ * k] (int32) is the byte at which packet k begins and entry [count] the row's byte count, so a length is a difference;
+ * d_counts[row] is the packet count.  Bytes and table entries behind those are not touched.  A call of n frames emits at most
+ * out_packets(n) = 398 n packets per row (one pending packet and 1191 / 3 walked ones per frame; a header needs four bytes left,
+ * so 396 walked ones are the most a frame reaches) and at most out_size(n) =
+ * 16392 + 1191 n bytes (every emitted byte is a distinct data byte of the call or a carried one); n <= 2^20 per call, so offsets
+ * fit int32.
+ * The loop runs in its closed form.  The walk of step 4 starts with nothing pending whatever came before, so a frame f that is no
+ * continuation frame determines by itself ctr_f, pkt_f, its walked packets data[pkt_f .. e_f) and its tail T_f: -1, or the residue
+ * length 1191 - e_f.  With cont_f = (ctr_(f-1) + 1 == ctr_f) and g the nearest frame before f that is no continuation frame (or
+ * the carried state), the incoming packetRead of f is in_f = T_g + 1191 (f - 1 - g) if T_g >= 0, cont holds for g + 1 .. f and the
+ * sum does not pass 16392 (at most 13 continuation frames fit), else -1; f emits a pending packet exactly when in_f >= 0 and
+ * in_f + pkt_f <= 16392, made of g's residue, the data areas of g + 1 .. f - 1 and data_f[0 .. pkt_f).  Two exclusive prefix sums
+ * over the row, of packets and of bytes, place every frame's output.
+ * process_batch_dev: asynchronous, three launches on hip_stream (fpkt_walk_kernel, fpkt_scan_kernel, fpkt_pack_kernel;
+ * qdsp_hip_last_kernel reports the last).  in_stride_bytes >= (nframes - 1) * frame_stride + 1195, out_stride_bytes >=
+ * out_size(nframes), offs_stride (in int32 entries) >= out_packets(nframes) + 1; rows may begin at any byte, d_offs is 4-byte
+ * aligned; d_in_counts: int32[nchan] on the device or NULL, row r has min(max(d_in_counts[r], 0), nframes) frames (qdsp_hip_rs's
+ * d_counts fits, so the two run on one stream with no host synchronisation); d_offs may be NULL and the offsets then go to a
+ * table the library owns (offs_dev: its pointer, its row stride in entries and the device counts, valid until a call with more
+ * frames than any before grows it; get_offsets copies up to cap + 1 entries of row `chan`, synchronises and returns the row's
+ * packet count); d_counts may be NULL, the counts are also kept in the handle (get_counts: int32[2][nchan], packets and bytes).
+ * d_out overlapping d_in, a short stride and nframes > 2^20 are QDSP_HIP_EINVAL.  nframes == 0 launches nothing, clears the
+ * counts and leaves the state alone; a row with a count of 0 keeps its state and its pending packet.  State and pending bytes are
+ * double-buffered.  Scratch is sized for max_block frames at create (a larger device call grows it and synchronises once).
+ * process_dev: the rows back to back, in_stride_bytes = nframes * frame_stride, out_stride_bytes = out_size(nframes), the
+ * library's offset table.  process / process_ex (nchan 1): `nframes` frames at `in`, `out` holds out_size(nframes) bytes; they
+ * return the packet count, the offsets are the library's table's; the output link is QDSP_HIP_LINK_HOST or _DEVICE only;
+ * nframes <= max_block where a side is on the host (else QDSP_HIP_ESIZE).
+ * get_state (pending: QDSP_HIP_FPKT_MAX_PACKET bytes, may be NULL), set_state (chan -1: all rows; packet_read -1, or 1 .. 16392
+ * with that many bytes at `pending`) and get_counts synchronise; reset restores the state after create.
+ * A packet-sync handle given to a qdsp_hip_rs_* entry point, or a decoder's to one of these, is QDSP_HIP_EINVAL. */
+#define QDSP_HIP_FPKT_FRAME_BYTES 1195
+#define QDSP_HIP_FPKT_MAX_PACKET 16392
+int qdsp_hip_fpkt_create(void** h, int device, int nchan, int max_block, int frame_stride);
+int64_t qdsp_hip_fpkt_out_size(void* h, int64_t nframes);
+int64_t qdsp_hip_fpkt_out_packets(void* h, int64_t nframes);
+int qdsp_hip_fpkt_frame_stride(void* h);
+int qdsp_hip_fpkt_process(void* h, const uint8_t* in, int nframes, uint8_t* out);
+int qdsp_hip_fpkt_process_ex(void* h, const void* in, int in_link, int nframes, void* out, int out_link);
+int qdsp_hip_fpkt_process_dev(void* h, const void* d_in, int64_t nframes, void* d_out, void* hip_stream);
+int qdsp_hip_fpkt_process_batch_dev(void* h, const void* d_in, int64_t nframes, int64_t in_stride_bytes, const int* d_in_counts, void* d_out,
+                                    int64_t out_stride_bytes, int* d_offs, int64_t offs_stride, int* d_counts, void* hip_stream);
+int qdsp_hip_fpkt_offs_dev(void* h, int** d_offs, int64_t* stride, int** d_counts);
+int qdsp_hip_fpkt_get_offsets(void* h, int chan, int* offs, int cap);
+int qdsp_hip_fpkt_get_counts(void* h, int* counts);
+int qdsp_hip_fpkt_get_state(void* h, int chan, uint32_t* last_counter, int* packet_read, uint8_t* pending);
+int qdsp_hip_fpkt_set_state(void* h, int chan, uint32_t last_counter, int packet_read, const uint8_t* pending);
+int qdsp_hip_fpkt_reset(void* h);
+void qdsp_hip_fpkt_destroy(void* h);
+
 /* ---- NOAA HRPT, TIP and HIRS demultiplexers : src/dsp/noaa/hrpt.h, src/dsp/noaa/tip.h ------------ */
 /* The three blocks behind a Deframer(110900): nchan channel-major rows per call, every result bit-exact.  Bits are numbered MSB
  * first from the start of an item, as readBits does (src/dsp/utils/bitstream.h); bits(o, l) is the l-bit field at bit o.  In all

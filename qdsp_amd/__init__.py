@@ -8,11 +8,13 @@ Layout
     ops.py       operator-level front-end used by tests/ and bench.py
     fec.py       forward error correction on the same plumbing: the Reed-Solomon decoder and FalconRS
     noaa.py      the NOAA HRPT tail on the same plumbing: HrptDemux, TipDemux, HirsDemux
+    falcon.py    the Falcon 9 tail on the same plumbing: FalconPacketSync
     sharding.py  time-axis chunking of one IQ stream over ranks with an (ntaps-1) halo
 
 Nothing in this package imports oracle/ (the CPU checker); there is no CPU fallback.
 """
 from . import capi  # noqa: F401
+from . import falcon  # noqa: F401
 from . import noaa  # noqa: F401
 
 __version__ = "0.1.0"

@@ -348,6 +348,22 @@ def load():
     sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, vp, vp, vp)
     sig(p + "_get_counts", i32, vp, C.POINTER(i32))
     sig(p + "_destroy", None, vp)
+    p = "qdsp_hip_fpkt"
+    sig(p + "_create", i32, pvp, i32, i32, i32, i32)
+    sig(p + "_out_size", i64, vp, i64)
+    sig(p + "_out_packets", i64, vp, i64)
+    sig(p + "_frame_stride", i32, vp)
+    sig(p + "_process", i32, vp, vp, i32, vp)
+    sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+    sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, vp, i64, vp, vp)
+    sig(p + "_offs_dev", i32, vp, pvp, C.POINTER(i64), pvp)
+    sig(p + "_get_offsets", i32, vp, i32, vp, i32)
+    sig(p + "_get_counts", i32, vp, C.POINTER(i32))
+    sig(p + "_get_state", i32, vp, i32, C.POINTER(C.c_uint32), C.POINTER(i32), vp)
+    sig(p + "_set_state", i32, vp, i32, C.c_uint32, i32, vp)
+    sig(p + "_reset", i32, vp)
+    sig(p + "_destroy", None, vp)
     p = "qdsp_hip_hrpt"
     sig(p + "_create", i32, pvp, i32, i32, i32)
     sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, vp, vp)

@@ -75,15 +75,19 @@ void* mapped_host_ptr(void* p) {
 }
 
 namespace {
+struct Entry {
+    OpKind kind;
+    int sub;
+};
 struct Registry {
     std::shared_mutex m;
-    std::unordered_map<const void*, OpKind> live;    // handle -> kind
+    std::unordered_map<const void*, Entry> live;     // handle -> {kind, sub}
 };
 Registry& registry() {
     static Registry* r = new Registry();    // (never destroyed: a handle may be released from a static destructor)
     return *r;
 }
-// h if it is in the table and `ok` takes its kind; h itself is not read
+// h if it is in the table and `ok` takes its entry; h itself is not read
 template <class F>
 StreamOp* lookup(void* h, F ok) {
     if (!h) return nullptr;
@@ -94,10 +98,10 @@ StreamOp* lookup(void* h, F ok) {
 }
 }  // namespace
 
-void stream_op_register(StreamOp* d, OpKind kind) {
+void stream_op_register(StreamOp* d, OpKind kind, int sub) {
     Registry& r = registry();
     std::unique_lock<std::shared_mutex> lk(r.m);
-    r.live[d] = kind;
+    r.live[d] = Entry{kind, sub};
 }
 
 void stream_op_unregister(StreamOp* d) {
@@ -106,12 +110,12 @@ void stream_op_unregister(StreamOp* d) {
     r.live.erase(d);
 }
 
-StreamOp* stream_op_lookup(void* h, OpKind kind) {
-    return lookup(h, [kind](OpKind k) { return k == kind; });
+StreamOp* stream_op_lookup(void* h, OpKind kind, int sub) {
+    return lookup(h, [kind, sub](const Entry& e) { return e.kind == kind && e.sub == sub; });
 }
 
 StreamOp* as_stream_op(void* h) {
-    return lookup(h, [](OpKind) { return true; });
+    return lookup(h, [](const Entry&) { return true; });
 }
 
 int stream_op_check(void** h, int device, int nchan, int max_block) {

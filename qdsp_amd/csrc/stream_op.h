@@ -1,5 +1,5 @@
 // stream_op.h -- what the handles of the per-row operators share (demod / deemp / level / stereo_fm / ff_agc / cagc / costas / mmcr /
-// rowfir / deframe / rs / noaa .hip, psk_chain.cpp):
+// rowfir / deframe / rs / fpkt / noaa .hip, psk_chain.cpp):
 // the head of the handle, the table that tells live handles and their kinds apart, the shape of create / free / the forwarding
 // entry points, and the one block-graph path (*_process_ex) and timing loop behind all of them.  Host code only (stream_op.cpp is built without an offload architecture, like ring.cpp); an operator supplies its launch
 // function and the bytes per sample of its two sides, and keeps its kernels, its launch-argument checks and its own state.
@@ -42,9 +42,10 @@ enum class OpKind : int {
     Chain,         // psk_chain.cpp (PSKDemod and MSKDemod are sub-kinds)
     Threshold,     // deframe.hip.h
     Deframer,      // deframe.hip.h
-    // The byte-stream tail.  Rs: rs.hip.h, the Reed-Solomon decoder and its FalconRS preset; Hrpt, Tip, Hirs: noaa.hip.h, the three
-    // NOAA demultiplexers behind it.  (They share a line on purpose: tests/test_psk_cpu.py reads one kind per line of this enum and
-    // pins the fourteen lines up to Rs; tests/test_noaa_cpu.py reads every enumerator and pins all seventeen.)
+    // The byte-stream tail.  Rs is the Falcon tail's kind: rs.hip.h, the Reed-Solomon decoder and its FalconRS preset, at sub-kind 0
+    // and fpkt.hip.h, FalconPacketSync, at sub-kind 1 (the table's, see below); Hrpt, Tip, Hirs: noaa.hip.h, the three NOAA
+    // demultiplexers.  (They share a line on purpose: tests/test_psk_cpu.py reads one kind per line of this enum and pins the
+    // fourteen lines up to Rs; tests/test_noaa_cpu.py reads every enumerator and pins all seventeen.)
     Rs, Hrpt, Tip, Hirs,
 };
 constexpr OpKind kLastOpKind = OpKind::Hirs;
@@ -78,17 +79,28 @@ int64_t launch_as(StreamOp* op, const void* d_in, int64_t count, int64_t in_stri
 // whole process) holds every live handle under its kind, entered as the last step of a successful create and taken out as the
 // first step of its free.  A lookup never reads the caller's pointer: a destroyed handle, a second destroy and foreign memory are
 // refused whatever they hold.  Lookups share the lock; only register and unregister exclude.
+// The table's value is {kind, sub}: a handle struct that shares its kind with another names its own `static constexpr int kSub`
+// (every other is at sub 0), and a lookup takes a handle only under both, so one unit's entry points refuse the other's handles.
 // (The engine, channelizer, math and ring handles -- kMagic, kChanMagic, kMathMagic, kRingMagic -- are no StreamOps and keep their magics.)
-void stream_op_register(StreamOp* d, OpKind kind);
+void stream_op_register(StreamOp* d, OpKind kind, int sub = 0);
 void stream_op_unregister(StreamOp* d);    // (a handle that is not in the table: nothing happens)
-// h if it is a live handle of `kind`
-StreamOp* stream_op_lookup(void* h, OpKind kind);
+// h if it is a live handle of `kind` and `sub`
+StreamOp* stream_op_lookup(void* h, OpKind kind, int sub = 0);
 // h if it is a live handle of any kind
 StreamOp* as_stream_op(void* h);
-// h as a T if it is a live handle of T's kind.  (Demod, Level and Chain check their sub-kind after it.)
+// T::kSub where T declares one, else 0
+template <class T, class = void>
+struct op_sub {
+    static constexpr int value = 0;
+};
+template <class T>
+struct op_sub<T, decltype((void)T::kSub)> {
+    static constexpr int value = T::kSub;
+};
+// h as a T if it is a live handle of T's kind and table sub-kind.  (Demod, Level and Chain check their in-struct sub-kind after it.)
 template <class T>
 T* as(void* h) {
-    return static_cast<T*>(stream_op_lookup(h, T::kKind));
+    return static_cast<T*>(stream_op_lookup(h, T::kKind, op_sub<T>::value));
 }
 
 // The argument checks every create begins with, after the operator's own: QDSP_HIP_EINVAL (h, nchan, max_block), then
@@ -125,7 +137,7 @@ int op_created(void** h, T* d, int rc) {
         Free(d);
         return rc;
     }
-    stream_op_register(d, T::kKind);
+    stream_op_register(d, T::kKind, op_sub<T>::value);
     *h = d;
     return 0;
 }
