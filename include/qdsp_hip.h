@@ -1097,6 +1097,49 @@ int qdsp_hip_synth_iq_dev(int device, void* d_out_iq, int64_t first_sample, int6
                           uint32_t seed, void* hip_stream);
 
 /* ---- introspection for the measurement harness ----------------------------------------- */
+/* ---- Viterbi decoder : src/libcorrect/convolutional (correct_convolutional_decode / _decode_soft) ---- */
+/* The decoder of libcorrect's convolutional codes over nchan channel-major rows of terminated frames; every count of this section
+ * is in FRAMES, every result bit-exact.  Stateless: nothing is carried from frame to frame or call to call, and there are no
+ * setters.  Per handle: rate (2 or 3), order (6 .. 9), `rate` polynomials below 2^order, sets (order + 7 .. 65536: the groups of
+ * `rate` symbols of a frame) and soft (0 / 1); anything else is QDSP_HIP_EINVAL.  A frame is frame_in_bytes = sets * rate soft
+ * bytes (0 a strong zero, 255 a strong one), or ceil(sets * rate / 8) bytes of hard bits, MSB first; it comes out as
+ * frame_out_bytes = (sets - order + 1) / 8 bytes, MSB first.  Each frame is decoded exactly as a FRESHLY CREATED
+ * correct_convolutional decodes it (correct_convolutional_decode_soft(conv, in, sets * rate, out) / _decode: a reused object carries
+ * its renormalisation counter from call to call; here the counter is 0 at every frame start):
+ *   table[r] = sum_i parity(r & poly[i]) << i over the `order`-bit register r; 2^(order-1) states; state j has predecessors
+ *   j >> 1 (low, label table[j]) and (j >> 1) | 2^(order-2) (high, label table[j | 2^(order-1)]).
+ *   Branch metric of label x: soft sum_i |y[i] - (x >> i & 1 ? 255 : 0)| (CORRECT_SOFT_LINEAR); hard popcount(x ^ g), bit i of g
+ *   the i-th bit of the group.  Path metrics are uint16_t and wrap: each sum is cut to 16 bits before it is compared.
+ *   Sets 1 .. order - 2 (warm-up): metric[j] = branch(table[j]) + metric[j >> 1] from zeros; no decision is recorded.  Set 0 is
+ *   read and counts for nothing: error_buffer_swap takes its read side before it moves its index, so the first swap after a reset
+ *   changes nothing and what set 0 wrote is overwritten by set 1.
+ *   Then sets - order + 1 processed steps.  Inner steps take the low predecessor when low <= high.  The last order - 1 steps (the
+ *   tail) take it only when low < high, and the k-th of them (k = 1 ..) considers only states that are multiples of skip = 2^k.
+ *   After processed step n: if n is a multiple of floor(65535 / (255 rate)) (128 / 85), the best state -- least metric among
+ *   every skip-th (1 outside the tail), the lowest index at the minimum -- is searched and its metric subtracted from all; if the
+ *   history holds 20 order steps (n = 20 order + 15 order m), a traceback from the best state (the same search, after the
+ *   subtraction) walks 5 order steps back and emits the 15 order decisions before them.  After the last step a traceback from
+ *   state 0 emits every decision still held.  Decision bits are written MSB first; the trailing partial byte is not stored.
+ *   (Where every searched metric is 65535 the C code reads an uninitialised index; here the lowest searched state is taken.)
+ * process_batch_dev: asynchronous, one launch (viterbi_decode_kernel, one wave per frame) on hip_stream.  in_stride_bytes >=
+ * nframes * frame_in_bytes, out_stride_bytes >= nframes * frame_out_bytes, rows and frames at any byte alignment; d_in_counts:
+ * int32[nchan] on the device or NULL, row r has min(max(d_in_counts[r], 0), nframes) frames (qdsp_hip_deframer's d_counts fits:
+ * the two run on one stream with no host synchronisation); the output of frames behind a row's count is not touched.
+ * nframes == 0 moves nothing.  Overlapping d_in / d_out, a short stride and nframes > 2^22 are QDSP_HIP_EINVAL.
+ * process_dev: the rows back to back.  process / process_ex (nchan 1): `nframes` whole frames at `in`; link codes as for the
+ * Reed-Solomon decoder; nframes <= max_block where a side is on the host (else QDSP_HIP_ESIZE); they return 0.
+ * The handle is known by its address, in a set of its own: every entry point refuses a handle of any other kind, a destroyed
+ * decoder, a second destroy and foreign memory, without reading the pointer.  qdsp_hip_last_kernel reports the launch. */
+int qdsp_hip_viterbi_create(void** h, int device, int nchan, int max_block, int rate, int order, const uint16_t* poly, int sets, int soft);
+int qdsp_hip_viterbi_frame_in_bytes(void* h);
+int qdsp_hip_viterbi_frame_out_bytes(void* h);
+int qdsp_hip_viterbi_process(void* h, const uint8_t* in, int nframes, uint8_t* out);
+int qdsp_hip_viterbi_process_ex(void* h, const void* in, int in_link, int nframes, void* out, int out_link);
+int qdsp_hip_viterbi_process_dev(void* h, const void* d_in, int64_t nframes, void* d_out, void* hip_stream);
+int qdsp_hip_viterbi_process_batch_dev(void* h, const void* d_in, int64_t nframes, int64_t in_stride_bytes, const int* d_in_counts, void* d_out,
+                                       int64_t out_stride_bytes, void* hip_stream);
+void qdsp_hip_viterbi_destroy(void* h);
+
 /* Name of the kernel the last process* call of this handle launched, and its launch
  * geometry; used by bench.py to pick the right row out of a rocprofv3 kernel trace. */
 int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* block, int* lds_bytes);

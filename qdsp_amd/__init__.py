@@ -9,6 +9,7 @@ Layout
     fec.py       forward error correction on the same plumbing: the Reed-Solomon decoder and FalconRS
     noaa.py      the NOAA HRPT tail on the same plumbing: HrptDemux, TipDemux, HirsDemux
     falcon.py    the Falcon 9 tail on the same plumbing: FalconPacketSync
+    viterbi.py   the Viterbi decoder of libcorrect's convolutional codes, batched over frames: ViterbiDecoder, Viterbi27
     sharding.py  time-axis chunking of one IQ stream over ranks with an (ntaps-1) halo
 
 Nothing in this package imports oracle/ (the CPU checker); there is no CPU fallback.
@@ -16,5 +17,6 @@ Nothing in this package imports oracle/ (the CPU checker); there is no CPU fallb
 from . import capi  # noqa: F401
 from . import falcon  # noqa: F401
 from . import noaa  # noqa: F401
+from . import viterbi  # noqa: F401
 
 __version__ = "0.1.0"

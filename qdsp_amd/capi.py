@@ -389,6 +389,15 @@ def load():
         sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
         sig(p + "_get_counts", i32, vp, C.POINTER(i32))
         sig(p + "_destroy", None, vp)
+    p = "qdsp_hip_viterbi"
+    sig(p + "_create", i32, pvp, i32, i32, i32, i32, i32, vp, i32, i32)
+    sig(p + "_frame_in_bytes", i32, vp)
+    sig(p + "_frame_out_bytes", i32, vp)
+    sig(p + "_process", i32, vp, vp, i32, vp)
+    sig(p + "_process_ex", i32, vp, vp, i32, i32, vp, i32)
+    sig(p + "_process_dev", i32, vp, vp, i64, vp, vp)
+    sig(p + "_process_batch_dev", i32, vp, vp, i64, i64, vp, vp, i64, vp)
+    sig(p + "_destroy", None, vp)
     sig("qdsp_hip_set_done_event", i32, vp, vp)
     sig("qdsp_hip_event_create", i32, i32, pvp)
     sig("qdsp_hip_event_destroy", i32, vp)

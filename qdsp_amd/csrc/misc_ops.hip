@@ -2,6 +2,7 @@
 // bench, completion events and the timing / introspection helpers of the harness.  Split out of qdsp_hip.hip in round 3.
 #include "engine.hip.h"
 #include "stream_op.h"
+#include "viterbi.hip.h"
 
 namespace qh {
 
@@ -177,6 +178,7 @@ int qdsp_hip_set_done_event(void* h, void* ev) {
 int qdsp_hip_last_kernel(void* h, char* name, int name_len, int* grid, int* block, int* lds) {
     const Launch* l = nullptr;
     if (StreamOp* d = as_stream_op(h)) l = &d->last;   // (the table first: a StreamOp is not read as something else)
+    else if (const Launch* v = viterbi_last(h)) l = v;   // (its own set of live addresses: viterbi.hip)
     else if (Chan* c = as_chan(h)) l = &c->last;
     else if (Engine* e = any_engine(h)) l = &e->last;
     if (!l) return QDSP_HIP_EINVAL;

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "qdsp_amd", "csrc")
 OUT = os.path.join(ROOT, "profiles", "r04_resource_usage.txt")
 UNITS = {"qdsp_hip": "", "chan_ops": "", "misc_ops": "", "fft_fir": "-fno-slp-vectorize", "fft1k_fir": "-fno-slp-vectorize", "chan": "-fno-slp-vectorize",
-         "pfb_dec": "-fno-slp-vectorize", "mf_dec": "", "rm_resamp": "", "fir_lat": "", "demod": "", "deemp": "", "level": "", "stereo_fm": "-fno-slp-vectorize", "ff_agc": "", "cagc": "", "costas": "", "mmcr": "", "rowfir": "-fno-slp-vectorize", "deframe": "", "rs": "", "fpkt": "", "noaa": ""}
+         "pfb_dec": "-fno-slp-vectorize", "mf_dec": "", "rm_resamp": "", "fir_lat": "", "demod": "", "deemp": "", "level": "", "stereo_fm": "-fno-slp-vectorize", "ff_agc": "", "cagc": "", "costas": "", "mmcr": "", "rowfir": "-fno-slp-vectorize", "deframe": "", "rs": "", "fpkt": "", "noaa": "", "viterbi": ""}
 
 
 def source_hash() -> str:
